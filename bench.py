@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- hot-path benchmark on MI355X (contract: round prompt section 4).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload = BASELINE.json configs[2] (SURVEY 8d "cfg3"): 50k spots x 3k genes x 5 time points, i.e.
@@ -19,8 +19,14 @@ problem (r mod 4, r mod 4 + 1); every step all-reduces the flat gradient buffer 
 beside the end of the backward pass); pair solves need no collective.  `value` = steps of all ranks / max-over-ranks
 wall time.
 
-Prints ONE JSON line on rank 0 -- at most LINE_LIMIT (6000) characters: the contract's keys, `roofline`, `cpu_baseline` and
-one-number summaries; the full record (texts, per-repeat timings, kernel tables) goes to gpurun_out/bench_detail_<N>gpu.json,
+A plain run measures the headline only: set-up, `--warmup` steps, ONE timed region of exactly `--steps` training steps
+(`value`, `ms_per_step`), the line.  `--full` adds everything else, as before: the Sinkhorn leg with its roofline, `--repeats`
+(default 5) timed regions, `roofline_train`, the whole-epoch block, the CPU baselines with their oracle parity checks, and
+the side file.  `--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (see
+dump_outputs), so that two builds can be compared output for output.
+
+Prints ONE JSON line on rank 0 -- at most LINE_LIMIT (6000) characters: the contract's keys, with --full also `roofline`,
+`cpu_baseline` and one-number summaries; the full record (texts, per-repeat timings, kernel tables) goes to a side file
 named in the line as `detail_file` (tests/test_bench_line_cpu.py).  `python bench.py --gpus N` with N > 1 and no WORLD_SIZE
 starts the N ranks itself (children, `python -m torch.distributed.run`), before anything touches the GPU.
 """
@@ -402,6 +408,36 @@ def write_detail(full, n_gpus):
     return None
 
 
+# ------------------------------------------------------------------------------ --dump-outputs
+
+DUMP_LIMIT_BYTES = 64 << 20     # every array of one dump together
+PARAM_SAMPLE = 1 << 23          # flat-parameter entries kept when the buffer holds more (32 MB of fp32; cfg3 has 16.1 M)
+
+
+def sample_index(n, k=PARAM_SAMPLE, seed=0):
+    """Sorted indices of a fixed, seeded sample of `k` of `n` entries (all of them when n <= k)."""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def dump_outputs(dirpath, arrays):
+    """{name: array} -> dirpath/<name>.npy; float64 stays float64, every other dtype is written as float32.  Refuses a
+    dump of more than DUMP_LIMIT_BYTES in all.  What a run dumps (rank 0, taken right after the last timed step):
+      train_losses   the loss vector that step returned (what training_step / GraphedStepper.step hand their caller);
+      train_params   the flat fp32 parameters that step left (FlatAdamW.flat_param), at sample_index(len) when larger;
+      sinkhorn_a/_b  the fp64 scalings a, b the timed Sinkhorn iterations left (when the Sinkhorn leg runs)."""
+    out = {k: np.ascontiguousarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32)
+           for k, v in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, more than the {DUMP_LIMIT_BYTES} allowed")
+    os.makedirs(dirpath, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(dirpath, k + ".npy"), a)
+    return sorted(out)
+
+
 # ------------------------------------------------------------------------------ main
 
 # BASELINE.json's single-GPU shapes (SURVEY 8: cfg2 = configs[1], cfg3 = configs[2], cfg5shape = configs[4]'s per-GPU
@@ -423,11 +459,17 @@ def parse_args(argv=None):
     ap.add_argument("--timepoints", type=int, default=None)
     ap.add_argument("--compute-dtype", default=None, choices=["bf16", "f32"])
     ap.add_argument("--ot-storage", default="f32", choices=["f32", "f64"])
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything, not only the headline: both legs (unless --leg), --repeats 5, roofline_train, "
+                         "the epoch block, CPU baselines and oracle parity checks, the side file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (bench.dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; value = their median")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; value = their median (default 1, with --full 5)")
     ap.add_argument("--cpu-steps", type=int, default=3, help="oracle training steps timed for cpu_baseline")
     ap.add_argument("--no-epoch", action="store_true", help="skip the whole-epoch block (100 steps + K-means + OT update)")
-    ap.add_argument("--leg", default="both", choices=["both", "train", "sinkhorn"])
+    ap.add_argument("--leg", default=None, choices=["both", "train", "sinkhorn"], help="default train, with --full both")
     ap.add_argument("--no-sinkhorn-parity", action="store_true",
                     help="skip the whole-solve oracle check of the Sinkhorn leg (about a minute of one host thread)")
     ap.add_argument("--preset", default="cfg3", choices=sorted(PRESETS),
@@ -439,6 +481,10 @@ def parse_args(argv=None):
                     help="launcher rehearsal: start the ranks, run the all-reduce-of-ones proof on the chosen backend, print the "
                          "line's header and exit -- no GPU is touched (tests/test_bench_line_cpu.py, SPADOT_BENCH_BACKEND=gloo)")
     args = ap.parse_args(argv)
+    if args.leg is None:
+        args.leg = "both" if args.full else "train"
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     pre = PRESETS[args.preset]
     args.custom = False
     for k in ("spots", "genes", "timepoints", "compute_dtype", "inducing"):
@@ -570,6 +616,7 @@ def _main(real_stdout, args):
     out = {"metric": METRIC, "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "data": "synthetic"}
     cdt = torch.bfloat16 if args.compute_dtype == "bf16" else torch.float32
+    dumps = {}                                      # --dump-outputs: name -> host array, written before the line
 
     # ========================================================================== training leg
     train_res = None
@@ -669,6 +716,11 @@ def _main(real_stdout, args):
                     last = step(args.warmup + i)
             barrier()
             regions.append(max_over_ranks(time.perf_counter() - t0))
+        if args.dump_outputs and rank == 0:         # before anything below steps the model on
+            idx = torch.as_tensor(sample_index(int(opt.count)), device=dev)
+            dumps["train_losses"] = last.detach().cpu().numpy()
+            dumps["train_params"] = opt.flat_param[idx].cpu().numpy()
+            del idx
         el = float(np.median(regions))
         b0 = dd["dataloaders"][sched[0][0]][sched[0][1]]
         train_res = {"value": world * args.steps / el, "ms_per_step": 1e3 * el / args.steps,
@@ -682,11 +734,12 @@ def _main(real_stdout, args):
                      "staged_graphs": bool(state["stepper"] is not None and state["stepper"].staged),
                      "bucketed_grad_exchange": bool(state["stepper"] is not None and state["stepper"].overlap)}
         train_res["units_in_schedule"] = len(sched)
-        train_res["roofline_train"] = roofline_train(dd, sched[0], cfg, G, args.compute_dtype, int(opt.count),
-                                                     train_res["ms_per_step"], tag="custom" if args.custom else args.preset)
-        if world == 1 and not args.no_epoch:
+        if args.full:
+            train_res["roofline_train"] = roofline_train(dd, sched[0], cfg, G, args.compute_dtype, int(opt.count),
+                                                         train_res["ms_per_step"], tag="custom" if args.custom else args.preset)
+        if args.full and world == 1 and not args.no_epoch:
             train_res["epoch"] = epoch_block(tu, model, opt, cfg, dd, state["stepper"], T, beta1, torch)
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
             t, bi = sched[0]
             train_res["cpu_baseline"], train_res["parity_check"] = cpu_train_steps(
                 model, opt, dd, cfg, tu, t, bi, t - 1, epoch, beta1, n_steps=max(1, args.cpu_steps))
@@ -705,25 +758,26 @@ def _main(real_stdout, args):
         info = solver.solve(OT_CFG)                 # whole 6-stage solve (first call: code objects load, attributes are set)
         torch.cuda.synchronize()
         solve_cold_s = time.perf_counter() - t0
-        t0 = time.perf_counter()
-        info2 = solver.solve(OT_CFG)                # the same solve again from scratch; leaves a converged state
-        torch.cuda.synchronize()
-        solve_s = time.perf_counter() - t0
-        assert list(info2.stage_iters) == list(info.stage_iters)
-        # one pair end to end, as compute_transport_map runs it (ot_solvers.py:95-121): cost matrix from the latents (sqeuclidean /
-        # exact median), the six-stage solve, the plan R / J left in HBM -- what full_solve_s leaves out is the cost setup
-        lx, ly = torch.as_tensor(lat_x, device=dev), torch.as_tensor(lat_y, device=dev)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        solver.set_cost_from_latents(lx, ly)
-        torch.cuda.synchronize()
-        cost_setup_s = time.perf_counter() - t0
-        solver.solve(OT_CFG)
-        plan_dev = solver.plan("torch")
-        torch.cuda.synchronize()
-        pair_e2e_s = time.perf_counter() - t0
-        del plan_dev, lx, ly
-        want_parity = rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_sinkhorn_parity
+        want_parity = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_sinkhorn_parity
+        if args.full:
+            t0 = time.perf_counter()
+            info2 = solver.solve(OT_CFG)                # the same solve again from scratch; leaves a converged state
+            torch.cuda.synchronize()
+            solve_s = time.perf_counter() - t0
+            assert list(info2.stage_iters) == list(info.stage_iters)
+            # one pair end to end, as compute_transport_map runs it (ot_solvers.py:95-121): cost matrix from the latents (sqeuclidean /
+            # exact median), the six-stage solve, the plan R / J left in HBM -- what full_solve_s leaves out is the cost setup
+            lx, ly = torch.as_tensor(lat_x, device=dev), torch.as_tensor(lat_y, device=dev)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            solver.set_cost_from_latents(lx, ly)
+            torch.cuda.synchronize()
+            cost_setup_s = time.perf_counter() - t0
+            solver.solve(OT_CFG)
+            plan_dev = solver.plan("torch")
+            torch.cuda.synchronize()
+            pair_e2e_s = time.perf_counter() - t0
+            del plan_dev, lx, ly
         # the solve's plan for the oracle check: taken NOW (before the timed iterations move a, b on) but kept on the device;
         # its 800 MB copy to pageable host memory follows the timed region (round 4: with that copy in front of it the region's
         # 20 x 10 iterations took 82.4 us each by the wall clock where the same 200 iterations between two HIP events take 75.9)
@@ -746,54 +800,58 @@ def _main(real_stdout, args):
         if solver.tau_flag(reset=True):
             raise RuntimeError("a scaling exceeded tau inside the timed Sinkhorn region: not a steady-state timing run")
         iters = args.steps * ITERS_PER_STEP
-        ev_ms = solver.run_iterations(OT_CFG, OT_CFG["epsilon"], iters, timed=True)      # the same iterations between two HIP events
-        # the same iterations inside the solver's real loop: + snapshot, duality-gap measure and one
-        # host sync every batch_size (5) iterations
-        ck_it, ck_ms = solver.run_checked(OT_CFG, OT_CFG["epsilon"], nbatches=max(4, args.steps), last_stage=True)
-        esize = 4 if args.ot_storage == "f32" else 8
-        kt = solver.time_kernels(OT_CFG, OT_CFG["epsilon"], reps=20)
-        geo = solver.fused_geometry()
-        # algorithmic bytes per launch = ONE sweep of the I x ld kernel matrix ("roofline");
-        # the fused pass's fp64 column partials (workgroups x ld x 8 B) are not counted
-        alg = float(I) * solver.ld * esize
-        dom = "fused_pass" if geo["vpt"] > 0 else max(("row_pass", "col_pass"), key=lambda k: kt[k])
-        ach = alg / (kt[dom] * 1e-3) / 1e9
+        if args.dump_outputs and rank == 0:         # the scalings the last timed iteration left
+            dumps["sinkhorn_a"], dumps["sinkhorn_b"] = solver.vector("a"), solver.vector("b")
         sk_res = {"value": world * iters / el, "unit": "Sinkhorn iters/s", "ms_per_iter": 1e3 * el / iters,
-                  "event_ms_per_iter": ev_ms / iters, "problem": f"{I}x{J}", "storage": args.ot_storage,
-                  "full_solve_s": solve_s, "full_solve_first_call_s": solve_cold_s, "full_solve_iters": int(sum(info.stage_iters)),
-                  "cost_setup_s": cost_setup_s, "pair_end_to_end_s": pair_e2e_s,
-                  "iters_per_s_with_convergence_checks": ck_it / (ck_ms * 1e-3),
-                  # `value` is the raw launch rate (no convergence measure); r01-r03 reported a region with a host
-                  # synchronisation every 10 iterations, so their 11.7-12.6 k are not like-for-like with r04+
-                  "value_is": "raw rate since r04 (no host sync inside the region); in-solve rate = iters_per_s_with_convergence_checks"}
-        roof = {"bound": "hbm", "kernel": "k_" + dom, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": ach / HBM_PEAK_GBS, "traffic": None, "alg_bytes_per_launch": alg,
-                "kernel_ms": kt, "fused_geometry": geo}
-        # HBM traffic per launch comes from separate rocprofv3 --pmc passes (FETCH_SIZE x2 for 16-byte/lane
-        # streams on gfx950, + WRITE_SIZE; MI355X_MICROARCH.md "HBM"): taken from the committed summary of the
-        # same workload, when there is one
-        pmc = newest_profile("sinkhorn_cfg3_f32_pmc_summary.csv")
-        if dom == "fused_pass" and I == 10000 and args.ot_storage == "f32" and pmc:
-            import csv
-            for row in csv.reader(open(pmc)):
-                if row and "k_fused_pass<float, 5, 2" in row[0]:
-                    traffic = (2.0 * float(row[1]) + float(row[3])) * 1024.0
-                    src = (f"replayed from {os.path.relpath(pmc, ROOT)} (separate rocprofv3 --pmc passes of this command with "
-                           "SPADOT_OT_SPEC_BATCHES=1, i.e. no launch that returns on the stop word: 2*FETCH_SIZE + WRITE_SIZE, "
-                           "bytes per launch) -- not measured in this run")
-                    if traffic >= alg:
-                        roof["traffic"], roof["traffic_source"] = traffic, src
-                    else:       # a kernel cannot move less than it must read: such a mean is polluted, not a result
-                        roof["traffic_source"] = (f"REJECTED: {src}; its mean of {traffic:.0f} bytes per launch is below the "
-                                                  f"{alg:.0f} algorithmic bytes (launches that did not sweep are in it)")
-            meta = newest_profile("sinkhorn_cfg3_f32_profile_meta.json")
-            if meta:
-                m = json.load(open(meta))
-                roof["profile_kernel_us"] = m.get("fused_pass_avg_us")
-                roof["profile_source_sha16"] = m.get("source_sha16")
-                roof["stale_profile"] = m.get("source_sha16") != source_fingerprint()
+                  "problem": f"{I}x{J}", "storage": args.ot_storage}
+        if args.full:
+            ev_ms = solver.run_iterations(OT_CFG, OT_CFG["epsilon"], iters, timed=True)      # the same iterations between two HIP events
+            # the same iterations inside the solver's real loop: + snapshot, duality-gap measure and one
+            # host sync every batch_size (5) iterations
+            ck_it, ck_ms = solver.run_checked(OT_CFG, OT_CFG["epsilon"], nbatches=max(4, args.steps), last_stage=True)
+            esize = 4 if args.ot_storage == "f32" else 8
+            kt = solver.time_kernels(OT_CFG, OT_CFG["epsilon"], reps=20)
+            geo = solver.fused_geometry()
+            # algorithmic bytes per launch = ONE sweep of the I x ld kernel matrix ("roofline");
+            # the fused pass's fp64 column partials (workgroups x ld x 8 B) are not counted
+            alg = float(I) * solver.ld * esize
+            dom = "fused_pass" if geo["vpt"] > 0 else max(("row_pass", "col_pass"), key=lambda k: kt[k])
+            ach = alg / (kt[dom] * 1e-3) / 1e9
+            sk_res.update({"event_ms_per_iter": ev_ms / iters,
+                           "full_solve_s": solve_s, "full_solve_first_call_s": solve_cold_s, "full_solve_iters": int(sum(info.stage_iters)),
+                           "cost_setup_s": cost_setup_s, "pair_end_to_end_s": pair_e2e_s,
+                           "iters_per_s_with_convergence_checks": ck_it / (ck_ms * 1e-3),
+                           # `value` is the raw launch rate (no convergence measure); r01-r03 reported a region with a host
+                           # synchronisation every 10 iterations, so their 11.7-12.6 k are not like-for-like with r04+
+                           "value_is": "raw rate since r04 (no host sync inside the region); in-solve rate = iters_per_s_with_convergence_checks"})
+            roof = {"bound": "hbm", "kernel": "k_" + dom, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": ach / HBM_PEAK_GBS, "traffic": None, "alg_bytes_per_launch": alg,
+                    "kernel_ms": kt, "fused_geometry": geo}
+            # HBM traffic per launch comes from separate rocprofv3 --pmc passes (FETCH_SIZE x2 for 16-byte/lane
+            # streams on gfx950, + WRITE_SIZE; MI355X_MICROARCH.md "HBM"): taken from the committed summary of the
+            # same workload, when there is one
+            pmc = newest_profile("sinkhorn_cfg3_f32_pmc_summary.csv")
+            if dom == "fused_pass" and I == 10000 and args.ot_storage == "f32" and pmc:
+                import csv
+                for row in csv.reader(open(pmc)):
+                    if row and "k_fused_pass<float, 5, 2" in row[0]:
+                        traffic = (2.0 * float(row[1]) + float(row[3])) * 1024.0
+                        src = (f"replayed from {os.path.relpath(pmc, ROOT)} (separate rocprofv3 --pmc passes of this command with "
+                               "SPADOT_OT_SPEC_BATCHES=1, i.e. no launch that returns on the stop word: 2*FETCH_SIZE + WRITE_SIZE, "
+                               "bytes per launch) -- not measured in this run")
+                        if traffic >= alg:
+                            roof["traffic"], roof["traffic_source"] = traffic, src
+                        else:       # a kernel cannot move less than it must read: such a mean is polluted, not a result
+                            roof["traffic_source"] = (f"REJECTED: {src}; its mean of {traffic:.0f} bytes per launch is below the "
+                                                      f"{alg:.0f} algorithmic bytes (launches that did not sweep are in it)")
+                meta = newest_profile("sinkhorn_cfg3_f32_profile_meta.json")
+                if meta:
+                    m = json.load(open(meta))
+                    roof["profile_kernel_us"] = m.get("fused_pass_avg_us")
+                    roof["profile_source_sha16"] = m.get("source_sha16")
+                    roof["stale_profile"] = m.get("source_sha16") != source_fingerprint()
         solver.close()
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
             sk_res["cpu_baseline"] = cpu_sinkhorn(I, J, budget_s=6.0 if want_parity else 10.0)
             if want_parity:
                 plan_first = plan_first_dev.cpu().numpy()
@@ -810,8 +868,8 @@ def _main(real_stdout, args):
         out["dtype_detail"] = (f"{args.compute_dtype} GAT branch + linears, f32 parameters/optimizer, f64 SVGP algebra; "
                                f"Sinkhorn {args.ot_storage} kernel matrix with f64 scalings")
         name = "custom shape" if args.custom else args.preset
-        out["config"] = {"workload": f"{name}: {T} time points x {N} spots x {G} genes, batch 512, k=30, {args.inducing} inducing points; "
-                                     f"Sinkhorn pair problem {N}x{N}",
+        out["config"] = {"workload": f"{name}: {T} time points x {N} spots x {G} genes, batch 512, k=30, {args.inducing} inducing points"
+                                     + (f"; Sinkhorn pair problem {N}x{N}" if sk_res is not None else ""),
                          "train": {k: v for k, v in (train_res or {}).items()
                                    if k not in ("cpu_baseline", "parity_check", "roofline_train", "epoch")},
                          "parallelism": "1 GPU" if world == 1 else (
@@ -832,13 +890,16 @@ def _main(real_stdout, args):
             out["sinkhorn"] = {k: v for k, v in sk_res.items() if k not in ("cpu_baseline", "parity_check")}
             if "parity_check" in sk_res:
                 out["parity_check_sinkhorn"] = sk_res["parity_check"]
-            out["roofline"] = roof
+            if roof is not None:
+                out["roofline"] = roof
         cb = (train_res or {}).get("cpu_baseline") or (sk_res or {}).get("cpu_baseline")
         if cb:
             out["cpu_baseline"] = cb
             if train_res and sk_res and "cpu_baseline" in sk_res and "cpu_baseline" in train_res:
                 out["cpu_baseline_sinkhorn"] = sk_res["cpu_baseline"]
-        _, line = compact_line(out, write_detail(out, world))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dumps)
+        _, line = compact_line(out, write_detail(out, world) if args.full else None)
         print(line, file=real_stdout, flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -63,6 +64,33 @@ def test_multi_rank_line_fits_too():
     full.pop("cpu_baseline")
     _, line = bench.compact_line(full, "gpurun_out/bench_detail_8gpu.json")
     assert len(line) < bench.LINE_LIMIT
+
+
+def test_a_plain_run_measures_the_headline_only():
+    """`bench.py --steps N` times ONE region of exactly N training steps; --full brings back both legs and five repeats;
+    an explicit --leg / --repeats holds in either mode."""
+    a = bench.parse_args(["--steps", "7"])
+    assert (a.full, a.leg, a.repeats, a.steps, a.dump_outputs) == (False, "train", 1, 7, None)
+    f = bench.parse_args(["--full"])
+    assert (f.full, f.leg, f.repeats) == (True, "both", 5)
+    e = bench.parse_args(["--leg", "sinkhorn", "--repeats", "3", "--dump-outputs", "out"])
+    assert (e.full, e.leg, e.repeats, e.dump_outputs) == (False, "sinkhorn", 3, "out")
+
+
+def test_dump_outputs_are_float_arrays_of_a_fixed_sample_within_the_limit(tmp_path):
+    n = 16136032                                                        # cfg3's flat parameter count
+    idx = bench.sample_index(n)
+    assert len(idx) == bench.PARAM_SAMPLE and (np.diff(idx) > 0).all() and 0 <= idx[0] and idx[-1] < n
+    assert np.array_equal(idx, bench.sample_index(n))                   # the same entries in every run
+    assert np.array_equal(bench.sample_index(1000), np.arange(1000))
+    names = bench.dump_outputs(str(tmp_path / "d"), {"losses": np.arange(7, dtype=np.float64),
+                                                     "params": np.ones(5, dtype=np.float16)})
+    assert names == ["losses", "params"]
+    assert np.load(tmp_path / "d" / "losses.npy").dtype == np.float64
+    assert np.load(tmp_path / "d" / "params.npy").dtype == np.float32
+    with pytest.raises(RuntimeError, match="dump-outputs"):
+        bench.dump_outputs(str(tmp_path / "e"), {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, dtype=np.float32)})
+    assert not (tmp_path / "e").exists()
 
 
 def _run(args, env_extra, timeout=240):

@@ -1,8 +1,6 @@
 """CPU: the C/numpy oracle against the reference's own outputs (tests/golden/ot_*.npz,
-made by oracle/gen_golden_ot.py) and, where it was built, against oracle/_ref/libot_ref.so
-(the reference's ot_func.cpp compiled as-is)."""
-import ctypes
-
+made by oracle/gen_golden_ot.py) and against the outputs of oracle/_ref/libot_ref.so (the reference's
+ot_func.cpp compiled as-is; tests/golden/ot_ref_library.npz, made by oracle/gen_golden_ref_lib.py)."""
 import numpy as np
 import pytest
 
@@ -106,35 +104,31 @@ def test_update_process_matches_reference(oracle_ot, tag, cur, thr):
 
 
 def test_against_compiled_reference_library(oracle_ot):
-    """Build-container check: oracle vs the reference's own C++ (oracle/_ref), random inputs."""
+    """Oracle vs the reference's own C++ (ot_func.cpp compiled as-is into oracle/_ref), seeded random inputs.  The
+    library's outputs are stored with their inputs in tests/golden/ot_ref_library.npz (oracle/gen_golden_ref_lib.py);
+    where oracle/_ref/libot_ref.so was built, the library is run again on the stored inputs and must reproduce them."""
+    from oracle import gen_golden_ref_lib as gen
+    g = load_golden("ot_ref_library.npz")
     L = oracle_ot.ref_lib()
-    if L is None:
-        pytest.skip("oracle/_ref/libot_ref.so not built")
-    rng = np.random.default_rng(7)
-    D = ctypes.POINTER(ctypes.c_double)
-    P = lambda x: x.ctypes.data_as(D)
-    cd = ctypes.c_double
-    for (m, n) in [(5, 9), (64, 33), (130, 257)]:
-        C = rng.uniform(0, 4, size=(m, n)); u = rng.normal(size=m) * .2; v = rng.normal(size=n) * .2
-        eps, l1, l2, tau = 0.2, 0.1, 5.0, 3.0
-        al1, al2 = l1 / (l1 + eps), l2 / (l2 + eps)
+    eps, l1, l2, tau = g["params"].tolist()
+    al1, al2 = l1 / (l1 + eps), l2 / (l2 + eps)
+    names = ("K", "R", "a", "b", "u_out", "v_out")
+    for (m, n) in g["shapes"].tolist():
+        tag = f"{m}x{n}"
+        C, u, v, p = (np.ascontiguousarray(g[f"{tag}_{k}"]) for k in ("C", "u", "v", "p"))
         dx, dy = np.ones(m) / m, np.ones(n) / n
-        p = rng.uniform(.5, 2, size=m); q = np.ones(n) * p.mean()
-        outs = []
-        for which in ("ref", "orc"):
-            K = np.zeros((m, n)); Kb = np.zeros((m, n)); R = np.zeros((m, n))
-            a, b, oa, ob = np.ones(m), np.ones(n), np.ones(m), np.ones(n)
-            uu, vv = u.copy(), v.copy()
-            if which == "ref":
-                L.update_k_double(P(K), P(Kb), P(C), P(uu), P(vv), cd(eps), m, n)
-                gap = L.update_process_double(P(R), P(a), P(b), P(oa), P(ob), P(K), P(Kb), P(C), P(dx),
-                                              P(dy), P(p), P(q), P(uu), P(vv), 5, 5, 5, cd(eps), cd(1e-8),
-                                              cd(tau), cd(l1), cd(l2), cd(al1), cd(al2), 0, 10 ** 7, m, n)
-            else:
-                oracle_ot.update_K(K, Kb, C, uu, vv, eps)
-                gap, _ = oracle_ot.update_process(R, a, b, oa, ob, K, Kb, C, dx, dy, p, q, uu, vv, 5, 5, 5,
-                                                  eps, 1e-8, tau, l1, l2, al1, al2, 0, 10 ** 7)
-            outs.append((K, R, a, b, uu, vv, gap))
-        for x, y in zip(outs[0][:-1], outs[1][:-1]):
-            np.testing.assert_allclose(y, x, rtol=1e-10, atol=1e-300)
-        assert not np.array_equal(outs[0][4], u)  # tau=3 forces an absorb on this input
+        q = np.ones(n) * p.mean()
+        K = np.zeros((m, n)); Kb = np.zeros((m, n)); R = np.zeros((m, n))
+        a, b, oa, ob = np.ones(m), np.ones(n), np.ones(m), np.ones(n)
+        uu, vv = u.copy(), v.copy()
+        oracle_ot.update_K(K, Kb, C, uu, vv, eps)
+        oracle_ot.update_process(R, a, b, oa, ob, K, Kb, C, dx, dy, p, q, uu, vv, 5, 5, 5,
+                                 eps, 1e-8, tau, l1, l2, al1, al2, 0, 10 ** 7)
+        want = {k: g[f"{tag}_{k}"] for k in names}
+        for k, x in zip(names, (K, R, a, b, uu, vv)):
+            np.testing.assert_allclose(x, want[k], rtol=1e-10, atol=1e-300, err_msg=f"{tag} {k}")
+        assert not np.array_equal(want["u_out"], u)  # tau=3 forces an absorb on this input
+        if L is not None:
+            live = gen.run_reference(L, C, u, v, p)
+            for k in names:
+                np.testing.assert_allclose(live[k], want[k], rtol=1e-10, atol=1e-300, err_msg=f"{tag} {k} (library)")

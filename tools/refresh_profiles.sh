@@ -2,7 +2,7 @@
 # Regenerates everything under profiles/rNN from ONE box (run through gpurun from the repo root):
 #   git rev-parse HEAD > .git_head; gpurun -- 'bash tools/refresh_profiles.sh r03' && cp gpurun_out/r03/summaries/* profiles/r03/
 # kernel trace + stats of both bench legs, the PMC passes of the Sinkhorn leg and of the GAT edge kernels (one counter
-# group per pass, nothing but the kernel trace beside them, as the guide's HBM recipe says), then the plain bench line.
+# group per pass, nothing but the kernel trace beside them, as the guide's HBM recipe says), then the full bench line.
 # Raw output goes to gpurun_out/, the summaries to profiles/.
 set -eo pipefail
 TAG=${1:-r03}
@@ -13,13 +13,13 @@ cd /tmp && export TMPDIR=/tmp
 # the Sinkhorn leg's profile runs without speculative batches: every k_fused_pass launch then sweeps the matrix (a launch
 # enqueued behind a converged batch returns on the stop word in ~5 us and would pull the per-launch means down)
 export SPADOT_OT_SPEC_BATCHES=1
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/sink -- python3 $R/bench.py --steps 20 --warmup 3 --repeats 1 --no-cpu-baseline --leg sinkhorn > $O/sink.json 2> $O/sink.log
-timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --steps 2 --warmup 1 --repeats 1 --no-cpu-baseline --leg sinkhorn > /dev/null 2> $O/pmc_fetch.log
-timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -- python3 $R/bench.py --steps 2 --warmup 1 --repeats 1 --no-cpu-baseline --leg sinkhorn > /dev/null 2> $O/pmc_write.log
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/sink -- python3 $R/bench.py --steps 20 --warmup 3 --full --repeats 1 --no-cpu-baseline --leg sinkhorn > $O/sink.json 2> $O/sink.log
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --steps 2 --warmup 1 --full --repeats 1 --no-cpu-baseline --leg sinkhorn > /dev/null 2> $O/pmc_fetch.log
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -- python3 $R/bench.py --steps 2 --warmup 1 --full --repeats 1 --no-cpu-baseline --leg sinkhorn > /dev/null 2> $O/pmc_write.log
 unset SPADOT_OT_SPEC_BATCHES
 # matrix-core utilisation of the training step's GEMM / GAT kernels: one counter pass, eager launches, nothing but the kernel trace beside it
 SPADOT_BENCH_NO_GRAPHS=1 timeout -k 10 400 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/mfma -- python3 $R/bench.py --steps 6 --warmup 2 --repeats 1 --no-epoch --no-cpu-baseline --leg train > /dev/null 2> $O/mfma.log
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/train -- python3 $R/bench.py --steps 40 --warmup 5 --repeats 1 --no-epoch --no-cpu-baseline --leg train > $O/train.json 2> $O/train.log
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/train -- python3 $R/bench.py --steps 40 --warmup 5 --full --repeats 1 --no-epoch --no-cpu-baseline --leg train > $O/train.json 2> $O/train.log
 # GAT edge kernels at the cfg3 batch shape (tools/gat_bench.py, 10k nodes, bf16): HBM fetch / write bytes and L2 hits
 export GAT_BENCH_REPS=6
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/gat_fetch -- python3 $R/tools/gat_bench.py > /dev/null 2> $O/gat_fetch.log
@@ -55,8 +55,8 @@ python3 tools/prof_timeline.py $O/train 0 3 > $P/train_cfg3_bf16_step_timeline_o
   echo "== tools/gemm_bench.py wgrad (csrc/gemm_wgrad_bf16.hip vs the library's g^T x, fp32 out)"
   PYTHONPATH=$R timeout -k 10 200 python3 tools/gemm_bench.py wgrad 2>/dev/null
 } > $P/gemm_probes.txt || true
-# the plain line (reads the summaries just written for roofline.traffic and roofline_train)
-timeout -k 10 900 python3 bench.py > $O/bench.json 2> $O/bench.log
+# the full line (reads the summaries just written for roofline.traffic and roofline_train)
+timeout -k 10 900 python3 bench.py --full > $O/bench.json 2> $O/bench.log
 tail -1 $O/bench.json > $P/bench_cfg3_1gpu.json
 # keep gpurun_out small enough to be merged back
 find $O -name '*kernel_trace.csv' -size +20M -delete
