@@ -318,6 +318,28 @@ int spadot_lloyd_step_groups(const double *X, double *C, const int *xoff, const 
                              int K, const double *tol, double *part, int *done, double *inertia, int update, int skip_done,
                              void *stream);
 
+/* The same iteration with a cluster count PER RESTART (the analyze stage's k = 4 .. 20 sweep, all data sets and all k in one
+ * launch pair): restart r belongs to group rgroup[r] (rows xoff[g] .. xoff[g] + npts[g] - 1 of X, stopping threshold tol[g])
+ * and has Kr[r] <= K_max clusters; C [R, K_max, D] keeps its first Kr[r] rows (the rest is padding, never read or written);
+ * part needs R * ceil(n_max / 256) * (K_max (D + 1) + 1) doubles.  A restart with Kr[r] == K_max sums in the order of
+ * spadot_lloyd_step_groups, bit for bit.  update / skip_done as there.  rgroup, Kr: int32 device arrays [R]. */
+int spadot_lloyd_step_sweep(const double *X, double *C, const int *xoff, const int *npts, int n_max, int R, const int *rgroup,
+                            const int *Kr, int K_max, int D, const double *tol, double *part, int *done, double *inertia, int update,
+                            int skip_done, void *stream);
+/* k-means++ seeding (sklearn's rule as in spadot_amd.kmeans.KMeansDevice: 2 + int(log k) candidates per further centre, drawn
+ * by potential; the candidate whose new potential is smallest wins, first on ties) for P problems in one launch, one workgroup
+ * each.  Problem p seeds pK[p] <= K_max centres on group pset[p] (rows xoff[g] .. xoff[g] + npts[g] - 1 of the centred data
+ * X, npts[g] <= n_max), starting from row pfirst[p]; round c (1 <= c < pK[p]) reads its uniforms from
+ * U[puoff[p] + (c - 1) * trials ...].  Candidate = first index whose prefix sum of the current distances is >= u * potential
+ * (clamped to n - 1); distances in the expanded form xsq - 2 x.c + csq clamped at 0.  The prefix sums are a fixed-order
+ * workgroup scan (bitwise reproducible), rounded in a different order from torch.cumsum: a candidate can differ from the torch
+ * path's only when a draw lies within rounding distance of a boundary.  Outputs: idx [P, K_max] int32 row indices (-1 in
+ * padding rows and for an invalid problem), centers [P, K_max, D] fp64 (zero padding).  closest: work space of P * n_max
+ * doubles.  D <= 32, K_max <= 32. */
+int spadot_kmeanspp_seed(const double *X, const int *xoff, const int *npts, int D, int P, const int *pset, const int *pK,
+                         const int *pfirst, const int *puoff, const double *U, int K_max, int n_max, double *closest, int *idx,
+                         double *centers, void *stream);
+
 /* Exact kk nearest neighbours of every point among all n points (self included), brute force in fp64, ordered by
  * (squared distance, index): out [n, kk] int32.  x [n, d] fp64, d <= 4, kk <= min(n, 128).  Replaces the host
  * NearestNeighbors call of _Cal_Spatial_Net (_utils.py:66-75) when the coordinates already live in HBM. */

@@ -1,0 +1,161 @@
+"""`analyze(args)`: mirror of the reference's SpaDOT/analyze.py -- the stage after `train`: K-means domains per time
+point (a fixed k per time point, or the adaptive elbow rule over k = 4 .. 20), the spot-level optimal transport between
+consecutive time points and its domain transition tables, and the plots.
+
+Arguments (the reference's): data, output_dir (default: the data file's directory), prefix ('adaptive_' when n_clusters is
+None and the prefix is empty), n_clusters (one k per time point, or None); added: device ('cuda:0'), write_tmaps (False).
+
+Input: the latent.npz `train` always writes (X, rows, timepoint, spatial), latent.h5ad where `anndata` is importable, or an
+in-memory object with .X, .obs['timepoint'], .obsm['spatial'].  Time points are taken sorted; days are their positions.
+
+Outputs in output_dir:
+  {prefix}domains.csv                          one row per input spot, in input order: row, timepoint, kmeans, pixel_x, pixel_y
+  {prefix}{tp}_WSS.csv                         (adaptive) clusters, wss, wss_diff, wss_diff_ratio, selected
+  {prefix}transition_table_{d}_{d+1}.csv/.npz  analyze_ot.write_transition_tables (also OT_g.txt, OT/tmap_*.npz on request);
+                                               .h5ad with the reference's names where anndata is importable
+  {prefix}{tp}_WSS_vs_Clusters.png, {prefix}{tp}_domains.png, {prefix}transition_dotplot_{d}_{d+1}.png   (with matplotlib)
+
+The whole K-means work of the stage (17 k x 10 restarts per time point in adaptive mode) is ONE kmeans.fit_sweep call on the
+MI355X; the reference refits the chosen k with the same seed, which reproduces the sweep's own fit for that k, so the labels
+are taken from the sweep.
+"""
+import os
+import time
+
+import numpy as np
+
+from .utils import _analyze_utils, _utils
+
+ADAPTIVE_KS = list(range(_analyze_utils.MIN_CLUSTERS, _analyze_utils.MAX_CLUSTERS + 1))
+
+
+def _dense(X):
+    return np.asarray(X.toarray() if hasattr(X, "toarray") else X)
+
+
+def _rows(adata, n):
+    obs = adata.obs
+    if isinstance(obs, dict):
+        return np.asarray(obs["row"]) if "row" in obs else np.arange(n)
+    return np.asarray(obs.index)                      # AnnData: obs_names
+
+
+def validate(n_clusters, counts, d):
+    """Checks of the outside input, before any device work.  counts: spots per (sorted) time point; d: latent dimension.
+    Returns the k values to fit per time point."""
+    from .kmeans import check_sweep_shape
+    T = len(counts)
+    if n_clusters is None:
+        for tp, n in counts.items():
+            if n < ADAPTIVE_KS[-1]:
+                raise ValueError(f"adaptive clustering fits k = {ADAPTIVE_KS[0]} .. {ADAPTIVE_KS[-1]}: time point {tp} has "
+                                 f"only {n} spots; give --n_clusters")
+        ks = [list(ADAPTIVE_KS) for _ in range(T)]
+    else:
+        n_clusters = [int(k) for k in n_clusters]
+        if len(n_clusters) != T:
+            raise ValueError(f"n_clusters has {len(n_clusters)} entries for {T} time points ({list(counts)}): give one k "
+                             f"per time point")
+        for (tp, n), k in zip(counts.items(), n_clusters):
+            if not 1 <= k <= min(n, 32):
+                raise ValueError(f"n_clusters = {k} for time point {tp} of {n} spots: k must be between 1 and "
+                                 f"min(spots, 32) = {min(n, 32)}")
+        ks = [[k] for k in n_clusters]
+    if d > 32:
+        raise ValueError(f"the latent has {d} dimensions; the device K-means supports at most 32")
+    check_sweep_shape(d, max(k for kt in ks for k in kt))
+    return ks
+
+
+def analyze(args):
+    print("Loading latent representations...")
+    adata, path = _utils.load_data(args.data)
+    if not getattr(args, "output_dir", None):
+        args.output_dir = os.path.dirname(path) if path else os.getcwd()
+    os.makedirs(args.output_dir, exist_ok=True)
+    if getattr(args, "prefix", None) is None:
+        args.prefix = ""
+    n_clusters = getattr(args, "n_clusters", None)
+    if n_clusters is None and args.prefix == "":
+        args.prefix = "adaptive_"
+    prefix, out = args.prefix, args.output_dir
+    device = getattr(args, "device", None) or "cuda:0"
+    write_tmaps = bool(getattr(args, "write_tmaps", False))
+
+    X = _dense(adata.X)
+    tp_all = np.asarray(adata.obs["timepoint"])
+    spatial = np.asarray(adata.obsm["spatial"])
+    rows = _rows(adata, X.shape[0])
+    tps = sorted(set(tp_all.tolist()))
+    masks = [tp_all == tp for tp in tps]
+    ks = validate(n_clusters, {tp: int(m.sum()) for tp, m in zip(tps, masks)}, int(X.shape[1]))
+
+    import torch
+    from . import analyze_ot, kmeans
+    from .ops import kmeans_assign
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("spadot_amd analyzes on the MI355X only (device 'cuda:N'); there is no CPU path")
+    timings = {}
+    t0 = time.perf_counter()
+    print("Clustering...")
+    latents = [np.ascontiguousarray(X[m]) for m in masks]
+    Xs = [torch.as_tensor(x, device=dev) for x in latents]
+    adaptive = n_clusters is None
+    res = kmeans.fit_sweep(Xs, ks, random_state=1993, n_init=10, labels_for=None if adaptive else True)
+    chosen, labels, wss_tables = [], [], []
+    for t, tp in enumerate(tps):
+        if adaptive:
+            wss = [res[t][k].inertia_ for k in ADAPTIVE_KS]
+            k = _analyze_utils.select_k(wss, timepoint=tp)
+            wss_tables.append(_analyze_utils.wss_table(wss, k))
+            cen = torch.as_tensor(res[t][k].cluster_centers_, device=dev)
+            lab = kmeans_assign(Xs[t].to(torch.float64), cen).cpu().numpy()   # the labels the sweep's fit of k gives
+        else:
+            k = ks[t][0]
+            lab = res[t][k].labels_
+        chosen.append(int(k))
+        labels.append(np.asarray(lab, dtype=np.int64))
+    torch.cuda.synchronize(dev)
+    timings["clustering"] = time.perf_counter() - t0
+
+    t0 = time.perf_counter()
+    print("Optimal transport...")
+    tables = analyze_ot.write_transition_tables(out, latents, labels, tps, prefix=prefix, device=device,
+                                                write_tmaps=write_tmaps)
+    torch.cuda.synchronize(dev)
+    timings["ot"] = time.perf_counter() - t0
+
+    t0 = time.perf_counter()
+    import pandas as pd
+    kcol = np.empty(X.shape[0], dtype=np.int64)
+    for m, lab in zip(masks, labels):
+        kcol[m] = lab
+    pd.DataFrame({"row": rows, "timepoint": tp_all, "kmeans": kcol, "pixel_x": spatial[:, 0],
+                  "pixel_y": spatial[:, 1]}).to_csv(os.path.join(out, prefix + "domains.csv"), index=False)
+    for tp, tab in zip(tps, wss_tables):
+        tab.to_csv(os.path.join(out, prefix + str(tp) + "_WSS.csv"), index=False)
+    names = [([f"{tps[d]}_{c}" for c in range(tab.shape[0])], [f"{tps[d + 1]}_{c}" for c in range(tab.shape[1])])
+             for d, tab in enumerate(tables)]
+    try:
+        import anndata
+        for d, (tab, (obs, var)) in enumerate(zip(tables, names)):     # the reference's files (tools/npz_to_h5ad.py's mapping)
+            anndata.AnnData(np.asarray(tab), obs=pd.DataFrame(index=obs), var=pd.DataFrame(index=var)).write_h5ad(
+                os.path.join(out, f"{prefix}transition_table_{d}_{d + 1}.h5ad"))
+    except ImportError:
+        pass
+    if _analyze_utils.have_matplotlib():
+        for t, tp in enumerate(tps):
+            if adaptive:
+                _analyze_utils.plot_wss(os.path.join(out, f"{prefix}{tp}_WSS_vs_Clusters.png"), ADAPTIVE_KS,
+                                        wss_tables[t]["wss"].tolist(), chosen[t])
+            _analyze_utils.plot_domains(os.path.join(out, f"{prefix}{tp}_domains.png"), spatial[masks[t], 0],
+                                        spatial[masks[t], 1], labels[t], tp)
+        for d, (tab, (obs, var)) in enumerate(zip(tables, names)):
+            _analyze_utils.plot_transition_dotplot(os.path.join(out, f"{prefix}transition_dotplot_{d}_{d + 1}.png"), tab, obs,
+                                                   var, d, d + 1)
+    else:
+        print("matplotlib not installed: no plots")
+    timings["writing"] = time.perf_counter() - t0
+    print("Results written to %s" % out)
+    return {"timepoints": tps, "labels": dict(zip(tps, labels)), "n_clusters": chosen, "tables": tables, "timings": timings}

@@ -8,6 +8,7 @@
 // gradient uses the transposed CSR instead of scatter-add), so results are bitwise reproducible.
 #include <hip/hip_runtime.h>
 #include <cmath>
+#include <climits>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -1187,11 +1188,15 @@ constexpr int LL_PTS = 256, LL_MAXK = 32, LL_MAXD = 32;
 // Groups (several data sets in one launch: the per-epoch K-means of ALL time points, _train_utils.py:255-269): restart r
 // belongs to group r / rpg, whose points are rows xoff[g] .. xoff[g] + npts[g] - 1 of X; n is then the LARGEST group (grid
 // and label stride); chunks past a group's end return at once.  xoff == nullptr: one data set of n rows, as before.
+// Sweep (the analyze stage's k = 4 .. 20 sweep, spadot_lloyd_step_sweep): Kr [R] gives restart r its own cluster count Kr[r]
+// <= K (K is then K_max, the padding of C [R, K_max, D] and of the partial-sum slots) and rgrp [R] its group; each restart
+// loops over its own Kr[r] only, so for Kr[r] == K the summation order is the uniform one.  Kr == rgrp == nullptr: as before.
 __global__ __launch_bounds__(LL_PTS) void k_lloyd_assign(const double *__restrict__ X, const double *__restrict__ C,
                                                          int n, int D, int K, double *__restrict__ part,
                                                          int *__restrict__ labels /* [R, n] or null */,
                                                          const int *__restrict__ xoff, const int *__restrict__ npts, int rpg,
-                                                         const int *__restrict__ skip_done) {
+                                                         const int *__restrict__ skip_done,
+                                                         const int *__restrict__ Kr, const int *__restrict__ rgrp) {
     extern __shared__ double ll_dyn[];           // K*D centres, then 256*D point coordinates
     double *s_c = ll_dyn, *s_x = ll_dyn + (size_t)K * D;
     __shared__ int s_lab[LL_PTS];
@@ -1202,12 +1207,13 @@ __global__ __launch_bounds__(LL_PTS) void k_lloyd_assign(const double *__restric
     const int stride_n = n;
     if (skip_done != nullptr && skip_done[r] != 0) return;      // a restart that has converged: nothing reads its partials again
     if (xoff != nullptr) {
-        const int g = r / rpg;
+        const int g = rgrp != nullptr ? rgrp[r] : r / rpg;
         n = npts[g];
         X += (size_t)xoff[g] * D;
         if (chunk * LL_PTS >= n) return;        // (uniform for the workgroup)
     }
-    for (int e = t; e < K * D; e += LL_PTS) s_c[e] = C[(size_t)r * K * D + e];
+    const int Kl = Kr != nullptr ? min(Kr[r], K) : K;  // this restart's cluster count; K is the padded stride
+    for (int e = t; e < Kl * D; e += LL_PTS) s_c[e] = C[(size_t)r * K * D + e];
     const int rows = min(LL_PTS, n - chunk * LL_PTS);
 #pragma unroll 4
     for (int e = t; e < rows * D; e += LL_PTS) s_x[e] = X[(size_t)chunk * LL_PTS * D + e];
@@ -1215,7 +1221,7 @@ __global__ __launch_bounds__(LL_PTS) void k_lloyd_assign(const double *__restric
     double best = INFINITY;
     int arg = -1;
     if (i < n) {
-        for (int k = 0; k < K; k++) {
+        for (int k = 0; k < Kl; k++) {
             double d2 = 0.0;
 #pragma unroll 4
             for (int c = 0; c < D; c++) { const double df = s_x[t * D + c] - s_c[k * D + c]; d2 += df * df; }
@@ -1226,7 +1232,7 @@ __global__ __launch_bounds__(LL_PTS) void k_lloyd_assign(const double *__restric
     s_lab[t] = arg;
     const double inertia = block_sum_d(i < n ? best : 0.0, s_red);       // (includes the barrier after s_lab)
     double *out = part + ((size_t)r * nchunk + chunk) * ((size_t)K * (D + 1) + 1);
-    for (int pq = t; pq < K * (D + 1); pq += LL_PTS) {
+    for (int pq = t; pq < Kl * (D + 1); pq += LL_PTS) {
         const int k = pq / (D + 1), c = pq - k * (D + 1);
         double acc = 0.0;
 #pragma unroll 8
@@ -1242,7 +1248,8 @@ __global__ __launch_bounds__(LL_PTS) void k_lloyd_assign(const double *__restric
 __global__ __launch_bounds__(256) void k_lloyd_update(const double *__restrict__ part, int nchunk, int D, int K,
                                                       double tol, double *__restrict__ C, int *__restrict__ done,
                                                       double *__restrict__ inertia, const int *__restrict__ npts, int rpg,
-                                                      const double *__restrict__ tolv, int skip_done) {
+                                                      const double *__restrict__ tolv, int skip_done,
+                                                      const int *__restrict__ Kr, const int *__restrict__ rgrp) {
     __shared__ double s_new[LL_MAXK * (LL_MAXD + 1)];
     __shared__ double s_red[16];
     const int r = blockIdx.x, t = threadIdx.x;
@@ -1250,11 +1257,12 @@ __global__ __launch_bounds__(256) void k_lloyd_update(const double *__restrict__
     const size_t stride = (size_t)K * (D + 1) + 1;
     const int slots = nchunk;                    // partial slots per restart (the largest group's chunk count)
     if (npts != nullptr) {
-        const int g = r / rpg;
+        const int g = rgrp != nullptr ? rgrp[r] : r / rpg;
         nchunk = (npts[g] + LL_PTS - 1) / LL_PTS;
         tol = tolv[g];
     }
-    for (int pq = t; pq < K * (D + 1); pq += 256) {
+    const int Kl = Kr != nullptr ? min(Kr[r], K) : K;
+    for (int pq = t; pq < Kl * (D + 1); pq += 256) {
         double acc = 0.0;
         for (int ch = 0; ch < nchunk; ch++) acc += part[((size_t)r * slots + ch) * stride + pq];
         s_new[pq] = acc;
@@ -1265,7 +1273,7 @@ __global__ __launch_bounds__(256) void k_lloyd_update(const double *__restrict__
     __syncthreads();
     double sh = 0.0;
     const bool frozen = done[r] != 0;
-    for (int e = t; e < K * D; e += 256) {
+    for (int e = t; e < Kl * D; e += 256) {
         const int k = e / D, c = e - k * D;
         const double cnt = s_new[k * (D + 1) + D], old = C[(size_t)r * K * D + e];
         const double nw = cnt > 0.0 ? s_new[k * (D + 1) + c] / cnt : old;
@@ -1276,6 +1284,147 @@ __global__ __launch_bounds__(256) void k_lloyd_update(const double *__restrict__
     if (t == 0) {
         inertia[r] = in;                     // inertia of the centres this iteration STARTED from
         if (!frozen && sh <= tol) done[r] = 1;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// k-means++ seeding for many problems in one launch (the analyze stage's sweep: every (data set, k, restart) triple is a
+// problem).  Block = problem p: the k - 1 selection rounds of KMeansDevice._init_centers (sklearn's rule: 2 + int(log k)
+// candidates drawn by potential, the one with the smallest new potential wins, first minimum on ties).  closest [n] lives
+// in a global work space row (it outgrows LDS at 50 000 points).  Per round:
+//   1. thread t owns the contiguous segment [t*seg, (t+1)*seg) of closest: its segment total, then a fixed-order
+//      (Hillis-Steele) scan of the 256 totals gives each segment's base;
+//   2. searchsorted (side left) of every draw u * pot: the thread walks its segment with a running sum from its base, the
+//      first index whose prefix is >= the draw is kept, the block minimum of those (an integer: order-free) is the
+//      candidate, clamped to n - 1;
+//   3. each candidate's potential sum_i min(closest_i, |x_i - c|^2), distance in the expanded form xsq - 2 x.c + csq
+//      clamped at 0 (the torch path's form), summed in a fixed order (block_sum_d);
+//   4. closest updated with the best candidate's distances (recomputed by the same function: the same bits).
+// No atomics on floating-point data: two runs are bitwise identical.  The prefix sums round in a different order from
+// torch.cumsum, so a candidate index can differ from the torch path's only when a draw lies within rounding distance of
+// a prefix boundary.
+constexpr int KPP_T = 256, KPP_MAXTR = 8;
+
+__device__ __forceinline__ int kpp_trials(int K) {      // 2 + int(log K) for 1 <= K <= 32 (e, e^2, e^3 = 2.72, 7.39, 20.09)
+    return 2 + (K >= 3) + (K >= 8) + (K >= 21);
+}
+
+__device__ __forceinline__ double kpp_d2(const double *__restrict__ xr, const double *c, double csq, int D) {
+    double xsq = 0.0, dot = 0.0;
+    for (int e = 0; e < D; e++) { const double v = xr[e]; xsq += v * v; dot += v * c[e]; }
+    return fmax(xsq - 2.0 * dot + csq, 0.0);
+}
+
+__global__ __launch_bounds__(KPP_T) void k_kmeanspp_seed(const double *__restrict__ X, const int *__restrict__ xoff,
+                                                         const int *__restrict__ npts, int D, const int *__restrict__ pset,
+                                                         const int *__restrict__ pK, const int *__restrict__ pfirst,
+                                                         const int *__restrict__ puoff, const double *__restrict__ U, int K_max,
+                                                         int n_max, double *__restrict__ closest, int *__restrict__ idx,
+                                                         double *__restrict__ centers) {
+    __shared__ double s_c[KPP_MAXTR * LL_MAXD];     // candidate rows (round 0: the first centre)
+    __shared__ double s_csq[KPP_MAXTR];
+    __shared__ double s_scan[KPP_T];
+    __shared__ double s_red[16];
+    __shared__ int s_cand[KPP_MAXTR];
+    const int p = blockIdx.x, t = threadIdx.x;
+    const int g = pset[p], K = pK[p], n = npts[g], first = pfirst[p];
+    int *ip = idx + (size_t)p * K_max;
+    double *cp = centers + (size_t)p * K_max * D;
+    for (int e = t; e < K_max; e += KPP_T) ip[e] = -1;                       // padding rows (and failed problems)
+    for (int e = t; e < K_max * D; e += KPP_T) cp[e] = 0.0;
+    if (K < 1 || K > K_max || n < 1 || n > n_max || first < 0 || first >= n) return;     // (uniform for the workgroup)
+    const double *Xg = X + (size_t)xoff[g] * D;
+    double *cl = closest + (size_t)p * n_max;
+    const double *Up = U + puoff[p];
+    const int trials = kpp_trials(K);
+    const int seg = (n + KPP_T - 1) / KPP_T, lo = min(t * seg, n), hi = min(lo + seg, n);
+
+    for (int e = t; e < D; e += KPP_T) s_c[e] = Xg[(size_t)first * D + e];
+    __syncthreads();
+    if (t == 0) {
+        double q = 0.0;
+        for (int e = 0; e < D; e++) q += s_c[e] * s_c[e];
+        s_csq[0] = q;
+        ip[0] = first;
+    }
+    for (int e = t; e < D; e += KPP_T) cp[e] = s_c[e];
+    __syncthreads();
+    double acc = 0.0;
+    for (int i = t; i < n; i += KPP_T) {
+        const double d = kpp_d2(Xg + (size_t)i * D, s_c, s_csq[0], D);
+        cl[i] = d;
+        acc += d;
+    }
+    double pot = block_sum_d(acc, s_red);
+    __syncthreads();                                 // (closest written by all threads before the segment walks)
+
+    for (int c = 1; c < K; c++) {
+        if (t < KPP_MAXTR) s_cand[t] = INT_MAX;
+        double ssum = 0.0;
+        for (int i = lo; i < hi; i++) ssum += cl[i];
+        s_scan[t] = ssum;
+        __syncthreads();
+        for (int off = 1; off < KPP_T; off <<= 1) {                      // inclusive scan of the segment totals
+            const double v = t >= off ? s_scan[t - off] : 0.0;
+            __syncthreads();
+            s_scan[t] += v;
+            __syncthreads();
+        }
+        double run = t > 0 ? s_scan[t - 1] : 0.0;
+        double rv[KPP_MAXTR];
+        int found[KPP_MAXTR];
+#pragma unroll
+        for (int j = 0; j < KPP_MAXTR; j++) {
+            rv[j] = j < trials ? Up[(size_t)(c - 1) * trials + j] * pot : 0.0;
+            found[j] = INT_MAX;
+        }
+        for (int i = lo; i < hi; i++) {
+            run += cl[i];
+#pragma unroll
+            for (int j = 0; j < KPP_MAXTR; j++)
+                if (j < trials && found[j] == INT_MAX && run >= rv[j]) found[j] = i;
+        }
+#pragma unroll
+        for (int j = 0; j < KPP_MAXTR; j++)
+            if (j < trials && found[j] != INT_MAX) atomicMin(&s_cand[j], found[j]);
+        __syncthreads();
+        for (int e = t; e < trials * D; e += KPP_T) {
+            const int j = e / D;
+            s_c[e] = Xg[(size_t)min(s_cand[j], n - 1) * D + (e - j * D)];
+        }
+        __syncthreads();
+        if (t < trials) {
+            double q = 0.0;
+            for (int e = 0; e < D; e++) q += s_c[t * D + e] * s_c[t * D + e];
+            s_csq[t] = q;
+        }
+        __syncthreads();
+        double lp[KPP_MAXTR];
+#pragma unroll
+        for (int j = 0; j < KPP_MAXTR; j++) lp[j] = 0.0;
+        for (int i = t; i < n; i += KPP_T) {
+            const double ci = cl[i];
+            const double *xr = Xg + (size_t)i * D;
+#pragma unroll
+            for (int j = 0; j < KPP_MAXTR; j++)
+                if (j < trials) lp[j] += fmin(kpp_d2(xr, s_c + j * D, s_csq[j], D), ci);
+        }
+        int best = 0;
+        double bpot = 0.0;
+#pragma unroll
+        for (int j = 0; j < KPP_MAXTR; j++) {
+            if (j < trials) {
+                const double pj = block_sum_d(lp[j], s_red);
+                if (j == 0 || pj < bpot) { bpot = pj; best = j; }
+            }
+        }
+        pot = bpot;
+        const double *cb = s_c + best * D;
+        const double csqb = s_csq[best];
+        for (int i = t; i < n; i += KPP_T) cl[i] = fmin(cl[i], kpp_d2(Xg + (size_t)i * D, cb, csqb, D));
+        for (int e = t; e < D; e += KPP_T) cp[(size_t)c * D + e] = cb[e];
+        if (t == 0) ip[c] = min(s_cand[best], n - 1);
+        __syncthreads();                             // closest, s_c and s_cand are reused by the next round
     }
 }
 
@@ -2691,10 +2840,10 @@ int spadot_lloyd_step(const double *X, double *C, int n, int D, int K, int R, do
     const int nchunk = (n + LL_PTS - 1) / LL_PTS;
     const size_t lds = sizeof(double) * ((size_t)K * D + (size_t)LL_PTS * D);      // <= 8 KB + 64 KB
     hipLaunchKernelGGL(k_lloyd_assign, dim3(nchunk, R), dim3(LL_PTS), lds, st_, X, (const double *)C, n, D, K, part, labels,
-                       (const int *)nullptr, (const int *)nullptr, 1, (const int *)nullptr);
+                       (const int *)nullptr, (const int *)nullptr, 1, (const int *)nullptr, (const int *)nullptr, (const int *)nullptr);
     if (update)
         hipLaunchKernelGGL(k_lloyd_update, dim3(R), dim3(256), 0, st_, (const double *)part, nchunk, D, K, tol, C, done, inertia,
-                           (const int *)nullptr, 1, (const double *)nullptr, 0);
+                           (const int *)nullptr, 1, (const double *)nullptr, 0, (const int *)nullptr, (const int *)nullptr);
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
@@ -2709,10 +2858,38 @@ int spadot_lloyd_step_groups(const double *X, double *C, const int *xoff, const 
     const int nchunk = (n_max + LL_PTS - 1) / LL_PTS, R = groups * rpg;
     const size_t lds = sizeof(double) * ((size_t)K * D + (size_t)LL_PTS * D);
     hipLaunchKernelGGL(k_lloyd_assign, dim3(nchunk, R), dim3(LL_PTS), lds, st_, X, (const double *)C, n_max, D, K, part,
-                       (int *)nullptr, xoff, npts, rpg, skip_done ? (const int *)done : (const int *)nullptr);
+                       (int *)nullptr, xoff, npts, rpg, skip_done ? (const int *)done : (const int *)nullptr, (const int *)nullptr,
+                       (const int *)nullptr);
     if (update)
         hipLaunchKernelGGL(k_lloyd_update, dim3(R), dim3(256), 0, st_, (const double *)part, nchunk, D, K, 0.0, C, done, inertia,
-                           npts, rpg, tol, skip_done);
+                           npts, rpg, tol, skip_done, (const int *)nullptr, (const int *)nullptr);
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+int spadot_lloyd_step_sweep(const double *X, double *C, const int *xoff, const int *npts, int n_max, int R, const int *rgroup,
+                            const int *Kr, int K_max, int D, const double *tol, double *part, int *done, double *inertia, int update,
+                            int skip_done, void *stream) {
+    if (n_max <= 0 || R <= 0 || R > 65535 || D <= 0 || D > LL_MAXD || K_max <= 0 || K_max > LL_MAXK) return -22;
+    if (!X || !C || !xoff || !npts || !rgroup || !Kr || !tol || !part || !done || !inertia) return -22;
+    if ((size_t)K_max * D + (size_t)LL_PTS * D > 7936) return -22;
+    hipStream_t st_ = (hipStream_t)stream;
+    const int nchunk = (n_max + LL_PTS - 1) / LL_PTS;
+    const size_t lds = sizeof(double) * ((size_t)K_max * D + (size_t)LL_PTS * D);
+    hipLaunchKernelGGL(k_lloyd_assign, dim3(nchunk, R), dim3(LL_PTS), lds, st_, X, (const double *)C, n_max, D, K_max, part,
+                       (int *)nullptr, xoff, npts, 1, skip_done ? (const int *)done : (const int *)nullptr, Kr, rgroup);
+    if (update)
+        hipLaunchKernelGGL(k_lloyd_update, dim3(R), dim3(256), 0, st_, (const double *)part, nchunk, D, K_max, 0.0, C, done,
+                           inertia, npts, 1, tol, skip_done, Kr, rgroup);
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+int spadot_kmeanspp_seed(const double *X, const int *xoff, const int *npts, int D, int P, const int *pset, const int *pK,
+                         const int *pfirst, const int *puoff, const double *U, int K_max, int n_max, double *closest, int *idx,
+                         double *centers, void *stream) {
+    if (P <= 0 || D <= 0 || D > LL_MAXD || K_max <= 0 || K_max > LL_MAXK || n_max <= 0) return -22;
+    if (!X || !xoff || !npts || !pset || !pK || !pfirst || !puoff || !U || !closest || !idx || !centers) return -22;
+    hipLaunchKernelGGL(k_kmeanspp_seed, dim3(P), dim3(KPP_T), 0, (hipStream_t)stream, X, xoff, npts, D, pset, pK, pfirst, puoff,
+                       U, K_max, n_max, closest, idx, centers);
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

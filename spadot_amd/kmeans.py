@@ -10,11 +10,12 @@ Parity: sklearn's fit is third-party and not pinned bit for bit (its own chunked
 the exact iteration count); what IS exact is the assignment rule -- labels are produced by the
 spadot_kmeans_assign kernel (nearest centre, first minimum wins), the same rule sklearn's predict applies.
 Selected by model_config['kmeans_backend']: 'device' (default) | 'sklearn' (the reference's host fit, the parity option).
+fit_sweep is the analyze stage's sweep over k (all time points, all k, all restarts at once: DESIGN 7b).
 """
 import numpy as np
 import torch
 
-from .ops import kmeans_assign, lloyd_steps, lloyd_steps_groups
+from .ops import kmeans_assign, kmeanspp_seed, lloyd_steps, lloyd_steps_groups, lloyd_steps_sweep
 
 
 class KMeansDevice:
@@ -274,3 +275,125 @@ def fit_many(Xs, n_clusters, random_state=1993, n_init=10, max_iter=300, tol=1e-
         plan = _PLANS[key] = _ManyPlan(dev, ns, int(Xs[0].shape[1]), int(n_clusters), int(n_init), int(random_state), max_iter,
                                        tol, check_every, Xs[0].dtype)
     return plan.run(Xs, use_graphs=use_graphs)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The analyze stage's sweep (reference _analyze_utils.py:42-105: KMeans(k, random_state=1993, n_init=10) for k = 4 .. 20 on
+# every time point, then the elbow rule): every (data set, k, restart) triple is one problem of ONE seeding launch
+# (spadot_kmeanspp_seed) and of one Lloyd launch pair per iteration (spadot_lloyd_step_sweep, a cluster count per restart).
+
+SWEEP_LDS_DOUBLES = 7936         # the Lloyd kernels keep K_max * D centres and 256 * D points in LDS
+
+
+def check_sweep_shape(d, k_max):
+    """ValueError unless the device sweep can fit k_max clusters in d dimensions (K <= 32, D <= 32, LDS budget)."""
+    if not 1 <= d <= 32:
+        raise ValueError(f"the device K-means supports data of 1 to 32 dimensions (got {d})")
+    if not 1 <= k_max <= 32:
+        raise ValueError(f"the device K-means supports 1 to 32 clusters (got {k_max})")
+    if (k_max + 256) * d > SWEEP_LDS_DOUBLES:
+        raise ValueError(f"{k_max} clusters in {d} dimensions exceed the device K-means' LDS budget "
+                         f"((k + 256) * d <= {SWEEP_LDS_DOUBLES})")
+
+
+def sweep_draws(n, k, random_state, n_init):
+    """The random draws of KMeansDevice(k, random_state, n_init).fit on n points: per restart the first centre's row and the
+    (k - 1) * (2 + int(log k)) uniforms of the selection rounds, round-major.  Returns (first int64 [n_init], U fp64
+    [n_init, (k - 1) * trials])."""
+    trials = 2 + int(np.log(k))
+    seeds = np.random.RandomState(int(random_state)).randint(np.iinfo(np.int32).max, size=int(n_init))
+    first = np.empty(int(n_init), dtype=np.int64)
+    U = np.empty((int(n_init), (k - 1) * trials), dtype=np.float64)
+    for r, sd in enumerate(seeds):
+        g = np.random.RandomState(int(sd))
+        first[r] = int(g.choice(n))
+        U[r] = g.uniform(size=(k - 1) * trials)       # the same stream as k - 1 calls of size `trials`
+    return first, U
+
+
+def fit_sweep(Xs, ks, random_state=1993, n_init=10, max_iter=300, tol=1e-4, check_every=8, labels_for=None):
+    """KMeansDevice(k, random_state, n_init).fit(Xs[t]) for every t and every k in ks[t], all at once.
+
+    Xs: list of [n_t, d] device tensors (one dimension and dtype); ks[t]: the k values to fit on set t.  Every k draws from
+    RandomState(random_state), as the reference creates every KMeans with random_state=1993, so each (set, k) gets exactly
+    the draws of KMeansDevice.fit.  Data centring and tol (tol * mean feature variance) follow fit_many.  One seeding launch
+    for all sum_t |ks[t]| * n_init restarts, Lloyd launch pairs for all of them (converged restarts skipped; one host sync
+    per `check_every` iterations), one pass measuring every restart's final inertia, best of n_init per (set, k) (first
+    minimum wins).  labels_for: (t, k) pairs whose labels are wanted (True: all), computed by the exact nearest-centre
+    kernel on the original coordinates.  Returns [ {k: KMeansResult} per set ]; labels_ is None where not asked for;
+    n_iter_ is the iteration count at the check where all restarts of that (set, k) had converged."""
+    T = len(Xs)
+    if len(ks) != T:
+        raise ValueError("fit_sweep needs one list of k values per data set")
+    if T == 0:
+        return []
+    dev = Xs[0].device
+    if not all(x.is_cuda and x.dim() == 2 and x.shape[1] == Xs[0].shape[1] and x.dtype == Xs[0].dtype for x in Xs):
+        raise ValueError("fit_sweep runs on the MI355X, on data sets of one dimension and dtype")
+    ks = [[int(k) for k in kt] for kt in ks]
+    ns = [int(x.shape[0]) for x in Xs]
+    d = int(Xs[0].shape[1])
+    k_max = max((k for kt in ks for k in kt), default=0)
+    if k_max == 0:
+        return [{} for _ in range(T)]
+    check_sweep_shape(d, k_max)
+    for t, kt in enumerate(ks):
+        for k in kt:
+            if not 1 <= k <= ns[t]:
+                raise ValueError(f"k = {k} clusters on data set {t} of {ns[t]} points")
+    R, n_max = int(n_init), max(ns)
+    f64, i32 = torch.float64, torch.int32
+    # centred data of all sets back to back, tol per set (fit_many's arithmetic)
+    offs = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+    X64s = [x.to(f64) for x in Xs]
+    means = [x.mean(0) for x in X64s]
+    Xall = torch.cat([x - m for x, m in zip(X64s, means)]).contiguous()
+    tolv = torch.stack([(Xall[offs[t]:offs[t + 1]] * Xall[offs[t]:offs[t + 1]]).sum(1).sum() / (ns[t] * d)
+                        for t in range(T)]) * float(tol)
+    xoff = torch.tensor(offs[:-1], dtype=i32, device=dev)
+    npts = torch.tensor(ns, dtype=i32, device=dev)
+    # problems in (set, k, restart) order; the host draws every restart's random numbers up front
+    pairs = [(t, k) for t in range(T) for k in ks[t]]
+    pset, pK, pfirst, puoff, Us = [], [], [], [], []
+    uoff = 0
+    for t, k in pairs:
+        first, U = sweep_draws(ns[t], k, random_state, R)
+        for r in range(R):
+            pset.append(t); pK.append(k); pfirst.append(int(first[r])); puoff.append(uoff)
+            Us.append(U[r])
+            uoff += U.shape[1]
+    if uoff >= np.iinfo(np.int32).max:
+        raise ValueError("too many random draws for one sweep")
+    Ucat = np.concatenate(Us) if uoff else np.zeros(1)
+    as_dev = lambda a, dt: torch.as_tensor(np.asarray(a), dtype=dt, device=dev)
+    pset, pK = as_dev(pset, i32), as_dev(pK, i32)
+    _, C = kmeanspp_seed(Xall, xoff, npts, n_max, pset, pK, as_dev(pfirst, i32), as_dev(puoff, i32), as_dev(Ucat, f64), k_max)
+    P = C.shape[0]
+    done = torch.zeros(P, dtype=i32, device=dev)
+    inertia = torch.zeros(P, dtype=f64, device=dev)
+    part = torch.empty(P * ((n_max + 255) // 256) * (k_max * (d + 1) + 1), dtype=f64, device=dev)
+    n_iter = np.zeros(len(pairs), dtype=np.int64)
+    it = 0
+    while it < max_iter:
+        steps = min(int(check_every), max_iter - it)
+        lloyd_steps_sweep(Xall, C, xoff, npts, n_max, pset, pK, tolv, done, inertia, part, steps, skip_done=True)
+        it += steps
+        pair_done = done.view(len(pairs), R).all(1).cpu().numpy()      # one host sync per `check_every` iterations
+        n_iter[(n_iter == 0) & pair_done] = it
+        if pair_done.all():
+            break
+    n_iter[n_iter == 0] = it
+    final = C.clone()                  # inertia of the FINAL centres: one assignment pass with every restart frozen
+    lloyd_steps_sweep(Xall, final, xoff, npts, n_max, pset, pK, tolv, torch.ones_like(done), inertia, part, 1)
+    inert = inertia.view(len(pairs), R)
+    best = torch.argmin(inert, dim=1)                                   # first minimum wins
+    ar = torch.arange(len(pairs), device=dev)
+    cen = C.view(len(pairs), R, k_max, d)[ar, best]                     # [pairs, K_max, d]
+    best_inertia = inert[ar, best].cpu().numpy()
+    want = set(pairs) if labels_for is True else set((int(t), int(k)) for t, k in (labels_for or ()))
+    out = [dict() for _ in range(T)]
+    for q, (t, k) in enumerate(pairs):
+        centers = cen[q, :k] + means[t]
+        labels = kmeans_assign(X64s[t], centers.contiguous()).cpu().numpy() if (t, k) in want else None
+        out[t][k] = KMeansResult(centers.cpu().numpy(), labels, float(best_inertia[q]), int(n_iter[q]))
+    return out

@@ -1860,6 +1860,35 @@ def lloyd_steps_groups(X, C, xoff, npts, n_max, groups, rpg, tol, done, inertia,
                "spadot_lloyd_step_groups")
 
 
+def lloyd_steps_sweep(X, C, xoff, npts, n_max, rgroup, Kr, tol, done, inertia, part, steps, update=True, skip_done=False):
+    """`steps` Lloyd iterations with a cluster count per restart (spadot_lloyd_step_sweep): X [sum n, D] fp64, C [R, K_max, D]
+    fp64, xoff / npts int32 [groups], rgroup / Kr int32 [R], tol fp64 [groups] device tensors; C / done / inertia updated in
+    place."""
+    D = X.shape[1]
+    R, K_max = C.shape[0], C.shape[1]
+    lib = model_lib()
+    for _ in range(steps):
+        _check(lib.spadot_lloyd_step_sweep(_p(X), _p(C), _p(xoff), _p(npts), int(n_max), R, _p(rgroup), _p(Kr), K_max, D, _p(tol),
+                                           _p(part), _p(done), _p(inertia), 1 if update else 0, 1 if skip_done else 0, _stream()),
+               "spadot_lloyd_step_sweep")
+
+
+def kmeanspp_seed(X, xoff, npts, n_max, pset, pK, pfirst, puoff, U, K_max):
+    """k-means++ seeding of P problems in one launch (spadot_kmeanspp_seed).  X [sum n, D] centred fp64, xoff / npts int32
+    [groups]; per problem int32 [P]: set, k, first-centre row, offset into the fp64 uniforms U.  Returns (idx [P, K_max] int32,
+    centers [P, K_max, D] fp64), padding rows -1 / 0."""
+    _need_cuda(X)
+    P, D = int(pset.shape[0]), int(X.shape[1])
+    dev = X.device
+    idx = torch.empty((P, K_max), dtype=torch.int32, device=dev)
+    centers = torch.empty((P, K_max, D), dtype=torch.float64, device=dev)
+    closest = torch.empty((P, int(n_max)), dtype=torch.float64, device=dev)
+    _check(model_lib().spadot_kmeanspp_seed(_p(X), _p(xoff), _p(npts), D, P, _p(pset), _p(pK), _p(pfirst), _p(puoff), _p(U),
+                                            int(K_max), int(n_max), _p(closest), _p(idx), _p(centers), _stream()),
+           "spadot_kmeanspp_seed")
+    return idx, centers
+
+
 def knn(coords, kk):
     """Indices [n, kk] (int32, device) of the kk nearest points of every point, itself included, ordered by
     (distance, index); brute force in fp64 on the device (include/spadot_model.h: spadot_knn)."""

@@ -13,23 +13,10 @@ import os
 import numpy as np
 import torch
 
-from .synthetic import SpatialData
 from .utils import _train_utils, _utils
 
 
-def _load(data):
-    if not isinstance(data, (str, os.PathLike)):
-        return data, None
-    path = os.path.abspath(data)
-    if path.endswith(".npz"):
-        z = np.load(path, allow_pickle=False)
-        return SpatialData(z["X"], z["timepoint"], z["spatial"]), path
-    try:
-        import anndata
-    except ImportError as e:
-        raise ImportError("reading .h5ad needs the `anndata` package (as the reference does); "
-                          "alternatively pass an .npz with X/timepoint/spatial or an in-memory object") from e
-    return anndata.read_h5ad(path), path
+_load = _utils.load_data
 
 
 def train(args):

@@ -1,0 +1,137 @@
+"""Host-side parts of the analyze stage: mirror of the reference's SpaDOT/utils/_analyze_utils.py.  The clustering itself
+runs on the device (spadot_amd.kmeans.fit_sweep); here are the elbow rule of Adaptive_clustering (:73-88) as a pure
+function, the WSS table, and the three plots (WSS curve :89-99, domains :140-164, transition dotplot :166-209), drawn with
+matplotlib's object API on an Agg canvas (no pyplot: global plotting state is left alone; seaborn is not needed)."""
+import numpy as np
+
+MIN_CLUSTERS, MAX_CLUSTERS, WSS_THRESHOLD = 4, 20, 0.1       # Adaptive_clustering's defaults
+
+
+def _curve(wss):
+    """(wss, d, ratio) as fp64 arrays: d[i] = wss[i-1] - wss[i] (NaN at i = 0), ratio[i] = d[i] / d[i+1] with numpy float
+    semantics (x / 0 -> +-inf, 0 / 0 -> NaN), NaN at the first and the last row."""
+    w = np.asarray(wss, dtype=np.float64).ravel()
+    n = w.size
+    d = np.full(n, np.nan)
+    ratio = np.full(n, np.nan)
+    if n > 1:
+        d[1:] = -np.diff(w)
+    if n > 2:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ratio[1:n - 1] = d[1:n - 1] / d[2:n]
+    return w, d, ratio
+
+
+def select_k(wss, min_clusters=MIN_CLUSTERS, max_clusters=MAX_CLUSTERS, wss_threshold=WSS_THRESHOLD, timepoint=None):
+    """The elbow rule of the reference's Adaptive_clustering (_analyze_utils.py:73-88).
+
+    wss[i] is the inertia of k = min_clusters + i, for k up to max_clusters.  With d_i = wss[i-1] - wss[i] and
+    ratio_i = d_i / d_{i+1} (undefined for the first and the last k; x / 0 = +-inf and 0 / 0 = NaN as in numpy), the rows
+    with d_i > wss_threshold * (max wss - min wss) are kept, and among them the k with the largest ratio wins; on ties the
+    first (pandas idxmax), NaN ratios are skipped.  When no kept row has a defined ratio the reference fails (idxmax gives
+    NaN, then a KeyError); here that is a ValueError naming the time point and showing the curve."""
+    w, d, ratio = _curve(wss)
+    if w.size != max_clusters - min_clusters + 1:
+        raise ValueError(f"select_k needs one WSS value per k = {min_clusters} .. {max_clusters} (got {w.size})")
+    thr = wss_threshold * (w.max() - w.min())
+    with np.errstate(invalid="ignore"):
+        ok = (d > thr) & ~np.isnan(ratio)
+    if not ok.any():
+        where = f" at time point {timepoint}" if timepoint is not None else ""
+        curve = ", ".join(f"{min_clusters + i}: {v:.6g}" for i, v in enumerate(w.tolist()))
+        raise ValueError(f"the WSS curve{where} has no elbow the adaptive rule can pick (WSS per k: {curve}); "
+                         f"give the number of clusters per time point with --n_clusters")
+    idx = np.flatnonzero(ok)
+    best = idx[int(np.argmax(ratio[idx]))]                # first maximum (inf included)
+    return int(min_clusters + best)
+
+
+def wss_table(wss, selected, min_clusters=MIN_CLUSTERS):
+    """The WSS table of one time point: columns clusters, wss, wss_diff, wss_diff_ratio, selected (a pandas DataFrame)."""
+    import pandas as pd
+    w, d, ratio = _curve(wss)
+    ks = np.arange(min_clusters, min_clusters + w.size)
+    return pd.DataFrame({"clusters": ks, "wss": w, "wss_diff": d, "wss_diff_ratio": ratio, "selected": ks == int(selected)})
+
+
+def have_matplotlib():
+    try:
+        import matplotlib  # noqa: F401
+        return True
+    except ImportError:
+        return False
+
+
+def _figure(figsize):
+    from matplotlib.backends.backend_agg import FigureCanvasAgg
+    from matplotlib.figure import Figure
+    fig = Figure(figsize=figsize)
+    FigureCanvasAgg(fig)
+    return fig
+
+
+def plot_wss(path, clusters, wss, k_selected):
+    """{prefix}{tp}_WSS_vs_Clusters.png (_analyze_utils.py:89-99)."""
+    clusters, wss = list(clusters), list(wss)
+    fig = _figure((10, 6))
+    ax = fig.add_subplot(1, 1, 1)
+    ax.plot(clusters, wss, marker="o")
+    ax.scatter(k_selected, wss[clusters.index(k_selected)], color="red", s=100, label="Selected Cluster")
+    ax.set_title("WSS vs Number of Clusters")
+    ax.set_xlabel("Number of Clusters")
+    ax.set_ylabel("WSS")
+    ax.set_xticks(clusters)
+    ax.grid()
+    fig.savefig(path)
+
+
+def plot_domains(path, pixel_x, pixel_y, labels, timepoint):
+    """{prefix}{tp}_domains.png: the spots coloured by K-means domain (_analyze_utils.py:140-164, there a seaborn scatter
+    with the tab10 palette)."""
+    import matplotlib
+    fig = _figure((5, 5))
+    ax = fig.add_subplot(1, 1, 1)
+    cmap = matplotlib.colormaps["tab10"]
+    labels = np.asarray(labels)
+    for i, c in enumerate(np.unique(labels).tolist()):
+        m = labels == c
+        ax.scatter(np.asarray(pixel_x)[m], np.asarray(pixel_y)[m], s=10, color=cmap(i % 10), label=str(c), linewidths=0)
+    ax.set_xlabel("pixel_x")
+    ax.set_ylabel("pixel_y")
+    ax.legend(title="kmeans", bbox_to_anchor=(1.05, 1), loc=2, borderaxespad=0.)
+    ax.set_title("Time point: {}".format(timepoint))
+    fig.tight_layout()
+    fig.savefig(path)
+
+
+def transition_min_prob(table):
+    """Element-wise minimum of the column-normalised and the row-normalised transition table (_analyze_utils.py:184-194)."""
+    t = np.asarray(table, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.minimum(t / t.sum(axis=0, keepdims=True), t / t.sum(axis=1, keepdims=True))
+
+
+def plot_transition_dotplot(path, table, obs_names, var_names, prev_day, next_day):
+    """{prefix}transition_dotplot_{d}_{d+1}.png (_analyze_utils.py:166-209): dot size and colour = transition_min_prob,
+    grey below 0.2."""
+    import matplotlib
+    from matplotlib.cm import ScalarMappable
+    v = transition_min_prob(table)
+    reds = matplotlib.colormaps["Reds"]
+    fig = _figure((v.shape[1] * 0.8, v.shape[0] * 0.8))
+    ax = fig.add_subplot(1, 1, 1)
+    for i in range(v.shape[0]):
+        for j in range(v.shape[1]):
+            value = v[i, j]
+            color = "grey" if value < 0.2 else reds(value)
+            ax.scatter(j, i, s=value * 500, c=[color], edgecolors="black", alpha=0.8)
+    ax.set_xticks(range(v.shape[1]))
+    ax.set_xticklabels(list(var_names), rotation=45, ha="right")
+    ax.set_yticks(range(v.shape[0]))
+    ax.set_yticklabels(list(obs_names))
+    ax.set_xlabel("{} Domains".format(next_day))
+    ax.set_ylabel("{} Domains".format(prev_day))
+    ax.set_title("Transition Probability Dotplot")
+    fig.colorbar(ScalarMappable(cmap="Reds"), label="Transition Probability", ax=ax)
+    fig.tight_layout()
+    fig.savefig(path)

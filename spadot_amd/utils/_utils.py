@@ -1,7 +1,7 @@
 """Small utilities of the training stage: mirror of the hot-path part of
 /root/reference/SpaDOT/utils/_utils.py (set_seed :22-32, load_model_config :38-50,
 _save_inducing_points :102-118).  The spatial graph (_Cal_Spatial_Net :52-100) lives in
-spadot_amd.graph without the dense adjacency."""
+spadot_amd.graph without the dense adjacency.  load_data is the input reader of both stages (train, analyze)."""
 import os
 import random
 
@@ -62,3 +62,26 @@ def _save_inducing_points(args, inducing_points_dict):
         df["timepoint"] = key
         frames.append(df)
     pd.concat(frames, ignore_index=True).to_csv(args.output_dir + os.sep + args.prefix + "inducing_points.csv", index=False)
+
+
+def load_data(data):
+    """The input of the train and analyze stages: a path to an .h5ad file (needs the `anndata` package, as in the
+    reference), a path to an .npz with arrays X, timepoint, spatial (and optionally rows: what train writes as latent.npz;
+    kept as obs['row']), or an in-memory object exposing .X, .obs['timepoint'], .obsm['spatial'].  Returns (data, absolute
+    path or None)."""
+    if not isinstance(data, (str, os.PathLike)):
+        return data, None
+    path = os.path.abspath(data)
+    if path.endswith(".npz"):
+        from ..synthetic import SpatialData
+        z = np.load(path, allow_pickle=False)
+        out = SpatialData(z["X"], z["timepoint"], z["spatial"])
+        if "rows" in z.files:
+            out.obs["row"] = np.asarray(z["rows"])
+        return out, path
+    try:
+        import anndata
+    except ImportError as e:
+        raise ImportError("reading .h5ad needs the `anndata` package (as the reference does); "
+                          "alternatively pass an .npz with X/timepoint/spatial or an in-memory object") from e
+    return anndata.read_h5ad(path), path

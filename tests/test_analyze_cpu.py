@@ -1,0 +1,168 @@
+"""The analyze stage's host side (no GPU): the elbow rule against the reference's pandas formulation, the command line,
+the prefix rule and the input checks that run before any device work, and the sweep's random draws."""
+import warnings
+
+import numpy as np
+import pandas as pd
+import pytest
+
+from spadot_amd import cli
+from spadot_amd.utils._analyze_utils import select_k, transition_min_prob, wss_table
+
+
+def _reference_rule(wss, min_clusters=4, max_clusters=20, wss_threshold=0.1):
+    """Independent restatement of _analyze_utils.py:73-88 (pandas); None where the reference fails."""
+    wss_diff = -np.diff(wss)
+    ratios = [wss_diff[i] / wss_diff[i + 1] for i in range(len(wss_diff) - 1)]
+    df = pd.DataFrame({"clusters": range(min_clusters, max_clusters + 1), "wss": wss,
+                       "wss_diff": [None] + list(wss_diff), "wss_diff_ratio": [None] + list(ratios) + [None]})
+    thr = wss_threshold * (df["wss"].max() - df["wss"].min())
+    f = df[df["wss_diff"] > thr]
+    try:
+        idx = f["wss_diff_ratio"].astype(float).idxmax()
+        return int(f["clusters"][idx])
+    except (KeyError, ValueError, TypeError):
+        return None
+
+
+def _curves(rng, count):
+    for i in range(count):
+        kind = i % 4
+        if kind == 0:       # monotone, elbow somewhere
+            d = rng.exponential(1.0, 16) * np.where(np.arange(16) < rng.integers(1, 16), 10.0, 1.0)
+            w = 100.0 + np.concatenate([[0.0], -np.cumsum(d)])[::1] + d.sum()
+        elif kind == 1:     # non-monotone
+            w = rng.normal(50.0, 10.0, 17)
+        elif kind == 2:     # plateaus: zero differences -> +-inf and NaN ratios
+            w = np.round(rng.normal(0.0, 1.0, 17).cumsum() * 0.7) + 20.0
+        else:               # few distinct values, mostly flat
+            w = rng.choice([1.0, 2.0, 5.0, 50.0], 17)
+        yield [float(v) for v in w]
+
+
+def test_select_k_matches_the_reference_rule_on_random_curves():
+    rng = np.random.default_rng(0)
+    checked = failed = 0
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        for w in _curves(rng, 400):
+            want = _reference_rule(w)
+            if want is None:
+                with pytest.raises(ValueError):
+                    select_k(w)
+                failed += 1
+            else:
+                assert select_k(w) == want, w
+                checked += 1
+    assert checked > 200 and failed > 0
+
+
+def test_select_k_hand_worked_cases():
+    assert select_k([100, 50, 20, 10, 9, 8.5, 8, 7.6, 7.3, 7.1, 7, 6.9, 6.8, 6.7, 6.6, 6.5, 6.4]) == 7
+    assert select_k([100] + [1] * 16) == 5                       # 99 / 0 = inf wins
+    with pytest.raises(ValueError, match="time point day3.*--n_clusters"):
+        select_k([100.0] * 16 + [0.0], timepoint="day3")        # the only kept row is the last k: no ratio
+    with pytest.raises(ValueError):
+        select_k([5.0] * 17)                                     # flat: nothing kept
+    with pytest.raises(ValueError):
+        select_k([1.0, 2.0])                                     # wrong length
+
+
+def test_wss_table_columns():
+    w = [100, 50, 20, 10, 9, 8.5, 8, 7.6, 7.3, 7.1, 7, 6.9, 6.8, 6.7, 6.6, 6.5, 6.4]
+    t = wss_table(w, 7)
+    assert list(t.columns) == ["clusters", "wss", "wss_diff", "wss_diff_ratio", "selected"]
+    assert t["clusters"].tolist() == list(range(4, 21)) and t["selected"].sum() == 1 and bool(t["selected"][3])
+    assert np.isnan(t["wss_diff"][0]) and t["wss_diff"][1] == 50 and t["wss_diff_ratio"][3] == pytest.approx(10.0)
+    assert np.isnan(t["wss_diff_ratio"][16])
+
+
+def test_transition_min_prob():
+    tab = np.array([[2.0, 0.0], [1.0, 1.0]])
+    np.testing.assert_allclose(transition_min_prob(tab), np.minimum(tab / tab.sum(0), tab / tab.sum(1)[:, None]))
+
+
+def test_cli_flags():
+    p = cli.build_parser()
+    a = p.parse_args(["analyze", "-i", "x.npz", "--n_clusters", "5,7,7,6"])
+    assert a.n_clusters == [5, 7, 7, 6] and a.data == "x.npz" and a.prefix == "" and a.device == "cuda:0"
+    assert a.output_dir is None and a.write_tmaps is False
+    a = p.parse_args(["analyze", "-i", "x.npz", "-o", "out", "--prefix", "p_", "--device", "cuda:1", "--write_tmaps"])
+    assert a.n_clusters is None and a.output_dir == "out" and a.prefix == "p_" and a.device == "cuda:1" and a.write_tmaps
+    a = p.parse_args(["train", "-i", "d.npz", "-o", "out", "--prefix", "t_", "--config", "c.yaml", "--device", "cuda:1",
+                      "--save_model"])
+    assert (a.data, a.output_dir, a.prefix, a.config, a.device, a.save_model) == ("d.npz", "out", "t_", "c.yaml", "cuda:1", True)
+    a = p.parse_args(["train"])
+    assert a.prefix == "" and a.device == "cuda:0" and a.save_model is False
+    with pytest.raises(SystemExit):
+        p.parse_args(["analyze"])                                # -i is required, as in the reference
+
+
+def test_cli_preprocess_exits_2(capsys):
+    with pytest.raises(SystemExit) as e:
+        cli.main(["preprocess", "-i", "x.h5ad"])
+    assert e.value.code == 2
+    assert "SpaDOT preprocess" in capsys.readouterr().err
+
+
+def test_cli_missing_input_messages(tmp_path):
+    with pytest.raises(SystemExit, match="latent representations does not exist"):
+        cli.main(["analyze", "-i", str(tmp_path / "none.npz")])
+    with pytest.raises(SystemExit, match="preprocessed data does not exist"):
+        cli.main(["train", "-i", str(tmp_path / "none.npz")])
+
+
+class _Args:
+    def __init__(self, **kw):
+        self.__dict__.update(dict(output_dir=None, prefix="", n_clusters=None, device="cuda:0"), **kw)
+
+
+def _latent_npz(path, counts, d=20, seed=0):
+    rng = np.random.default_rng(seed)
+    n = sum(counts)
+    np.savez_compressed(path, X=rng.normal(size=(n, d)).astype(np.float32), rows=np.arange(n),
+                        timepoint=np.repeat(np.arange(len(counts)), counts), spatial=rng.uniform(size=(n, 2)))
+
+
+def test_analyze_prefix_rule_and_input_checks_fail_before_the_device(tmp_path, monkeypatch):
+    import torch
+    from spadot_amd.analyze import analyze
+
+    def no_device(*a, **k):
+        raise AssertionError("device touched before the input checks")
+    monkeypatch.setattr(torch, "as_tensor", no_device)
+    f = tmp_path / "latent.npz"
+    _latent_npz(f, [30, 12, 25])
+    a = _Args(data=str(f))
+    with pytest.raises(ValueError, match="time point 1 has only 12 spots"):     # adaptive needs 20 spots
+        analyze(a)
+    assert a.prefix == "adaptive_" and a.output_dir == str(tmp_path)
+    a = _Args(data=str(f), prefix="mine_")
+    with pytest.raises(ValueError):
+        analyze(a)
+    assert a.prefix == "mine_"
+    a = _Args(data=str(f), n_clusters=[3, 3])
+    with pytest.raises(ValueError, match="2 entries for 3 time points"):
+        analyze(a)
+    assert a.prefix == ""
+    with pytest.raises(ValueError, match="n_clusters = 13 for time point 1 of 12 spots"):
+        analyze(_Args(data=str(f), n_clusters=[3, 13, 3]))
+    with pytest.raises(ValueError, match="between 1 and"):
+        analyze(_Args(data=str(f), n_clusters=[0, 3, 3]))
+    g = tmp_path / "wide.npz"
+    _latent_npz(g, [30, 30], d=40)
+    with pytest.raises(ValueError, match="40 dimensions"):
+        analyze(_Args(data=str(g), n_clusters=[3, 3]))
+
+
+def test_sweep_draws_are_those_of_the_single_fit():
+    from spadot_amd.kmeans import sweep_draws
+    for n, k in ((257, 4), (1000, 7), (50, 20), (10, 1)):
+        first, U = sweep_draws(n, k, 1993, 10)
+        trials = 2 + int(np.log(k))
+        seeds = np.random.RandomState(1993).randint(np.iinfo(np.int32).max, size=10)
+        for r, s in enumerate(seeds):          # KMeansDevice._init_centers' call order
+            g = np.random.RandomState(int(s))
+            assert first[r] == int(g.choice(n))
+            want = np.concatenate([g.uniform(size=trials) for _ in range(1, k)]) if k > 1 else np.zeros(0)
+            np.testing.assert_array_equal(U[r], want)
