@@ -15,6 +15,7 @@
  *   spadot_vae_*       model/SpaDOT.py:78-93 (reparameterisation, GAT KL, reconstruction, alignment)
  *   spadot_kmeans_*    utils/_train_utils.py:240-253 (loss) and sklearn KMeans.predict (labels, :266-269)
  *   spadot_adamw_*     utils/_train_utils.py:214-217 (clip_grad_norm_(0.3) + AdamW.step)
+ *   spadot_pre_*, spadot_sparkx_*  utils/_utils.py:121-414 (SPARK-X) and utils/_preprocess_utils.py:11-49 (the preprocess stage)
  */
 #ifndef SPADOT_MODEL_H
 #define SPADOT_MODEL_H
@@ -589,6 +590,37 @@ int spadot_adamw_step(float *param, const float *grad, float *exp_avg, float *ex
 int spadot_adamw_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq,
                           const float *sumsq, long long count, double lr, double beta1, double beta2,
                           double eps, double weight_decay, double max_norm, int *step_dev, void *stream);
+
+/* ---------------------------------------------------------------- preprocess stage (csrc/preprocess.hip)
+ * SPARK-X gene statistics and the log-normalise + scale of the output (SpaDOT/utils/_utils.py:121-414,
+ * _preprocess_utils.py:11-49).  Counts are fp32 in CSR (indptr [n+1], cidx, val: spots x genes) and CSC (colptr [G+1], ridx
+ * sorted within each column, val: genes x spots), rows in output order: time point t owns rows [tp_off[t], tp_off[t+1]).
+ * Every sum is fp64, owned by one wavefront in a fixed order (no atomics: bitwise repeatable).
+ *
+ * gene_detect:  cnt[t, g] = #{rows of t: x >= thr}, colsum[t, g] = sum of x over the rows of t              (CSC)
+ * row_total:    total[r] = sum of x[r, g] over the genes with mask[t(r), g] != 0, rows tp_off[0] .. + nrows   (CSR)
+ * sparkx_moments: per pair p = (pair_t, pair_g): mom[p, 24] = sum y, sum y^2, sum y * xt[rowmap[r], 0 .. 21]; xt [*, 22]
+ *               fp64 centred kernel coordinates of the kept spots, rowmap[r] = its row or -1                  (CSC)
+ * sparkx_pvals: per pair: stat[p, 11], pval[p, 11] (two-term chi^2_1 survival, trapezoid on `nodes` points; ylam = 0 -> 1),
+ *               comb[p] (ACAT).  inv [T, 11, 4] = (X^T X)^-1, lam [T, 11, 2] its eigenvalues of X^T X (X^T X)^-1,
+ *               nkeep[t] kept spots
+ * lognorm_stats: v = log1p(x * target / total[r]); mean[t, j], std[t, j] (ddof 1, 0 -> 1) of column cols[j] over the rows
+ *               of t                                                                                             (CSC)
+ * scale_write:  out[(r - tp_off[0]) * S + colpos[g]] = clip((v - mean) / std) as fp32 (clip 0: none), dense rows
+ *               tp_off[0] .. + nrows                                                                             (CSR) */
+int spadot_pre_gene_detect(const long long *colptr, const int *ridx, const float *val, const int *tp_off, int T, int G,
+                           double thr, int *cnt, double *colsum, void *stream);
+int spadot_pre_row_total(const long long *indptr, const int *cidx, const float *val, const int *tp_off, int T, int G,
+                         const unsigned char *mask, int nrows, double *total, void *stream);
+int spadot_sparkx_moments(const long long *colptr, const int *ridx, const float *val, const int *tp_off, int P,
+                          const int *pair_t, const int *pair_g, const int *rowmap, const double *xt, double *mom, void *stream);
+int spadot_sparkx_pvals(const double *mom, int P, const int *pair_t, const int *nkeep, const double *inv, const double *lam,
+                        int nodes, double *stat, double *pval, double *comb, void *stream);
+int spadot_pre_lognorm_stats(const long long *colptr, const int *ridx, const float *val, const int *tp_off, int T, int S,
+                             const int *cols, const double *total, double target, double *mean, double *stdv, void *stream);
+int spadot_pre_scale_write(const long long *indptr, const int *cidx, const float *val, const int *tp_off, int T, int S,
+                           const int *colpos, const double *total, double target, const double *mean, const double *stdv,
+                           double clip, int nrows, float *out, void *stream);
 
 #ifdef __cplusplus
 }

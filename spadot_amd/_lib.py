@@ -259,6 +259,12 @@ def model_lib():
         "spadot_adamw_range_dev": [vp, vp, vp, vp, ll, ll, cd, cd, cd, cd, cd, cd, vp, vp, vp, ctypes.POINTER(WeightImages), vp],
         "spadot_adamw_step": [vp, vp, vp, vp, vp, ll, cd, cd, cd, cd, cd, cd, ci, vp],
         "spadot_adamw_step_dev": [vp, vp, vp, vp, vp, ll, cd, cd, cd, cd, cd, cd, vp, vp],
+        "spadot_pre_gene_detect": [vp, vp, vp, vp, ci, ci, cd, vp, vp, vp],
+        "spadot_pre_row_total": [vp, vp, vp, vp, ci, ci, vp, ci, vp, vp],
+        "spadot_sparkx_moments": [vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp],
+        "spadot_sparkx_pvals": [vp, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp],
+        "spadot_pre_lognorm_stats": [vp, vp, vp, vp, ci, ci, vp, vp, cd, vp, vp, vp],
+        "spadot_pre_scale_write": [vp, vp, vp, vp, ci, ci, vp, vp, cd, vp, vp, cd, ci, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)

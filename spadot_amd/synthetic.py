@@ -53,3 +53,48 @@ def make_dataset(n_timepoints, spots_per_tp, n_genes, seed=1993, shuffle=True):
     data = SpatialData(np.concatenate(Xs), np.concatenate(tps), np.concatenate(locs))
     data.obs["domain"] = np.concatenate(doms)
     return data
+
+
+def make_raw_counts(spots_per_tp=(400, 1200, 2000), n_genes=1500, n_modules=4, genes_per_module=30, n_rare=5, seed=1993,
+                    shuffle=True):
+    """Raw counts for the preprocess stage: per time point negative-binomial counts (dispersion 5) on the jittered grid of
+    make_timepoint.  Genes 0 .. n_modules * genes_per_module - 1 are spatially patterned, module m sharing one smooth
+    pattern of the time point's normalised coordinates (a Gaussian bump for even m, a stripe for odd m); the rest are null
+    genes with a constant mean.  The last n_rare genes are detected in fewer than 5 spots of every time point, the last null
+    gene before them is zero in the first time point (a zero-variance gene there), and one spot per time point has a zero
+    total.  Returns a SpatialData whose X is dense float32 counts, with var_names and uns['module'] (module per gene, -1 for
+    null genes)."""
+    rng = np.random.default_rng(seed)
+    n_tp = len(spots_per_tp)
+    n_sp = n_modules * genes_per_module
+    module = np.full(n_genes, -1)
+    module[:n_sp] = np.repeat(np.arange(n_modules), genes_per_module)
+    base = np.exp(rng.uniform(np.log(0.3), np.log(3.0), size=n_genes))
+    Xs, tps, locs = [], [], []
+    for t, n in enumerate(spots_per_tp):
+        xy, _, _ = make_timepoint(int(n), 1, seed + 17 * t, shuffle=shuffle)
+        u = (xy - xy.min(0)) / np.maximum(np.ptp(xy, 0), 1e-12)
+        pats = []
+        for m in range(n_modules):
+            c = np.array([0.25 + 0.5 * ((m // 2) % 2), 0.25 + 0.5 * (m % 2)])
+            if m % 2 == 0:
+                pats.append(np.exp(-((u - c) ** 2).sum(1) / (2 * 0.15 ** 2)))
+            else:
+                pats.append(0.5 * (1 + np.sin(2 * np.pi * (u[:, 0] * 1.5 + 0.3 * m))))
+        mu = np.tile(base, (int(n), 1))
+        for m in range(n_modules):
+            sel = module == m
+            mu[:, sel] = base[sel][None, :] * np.exp(2.0 * pats[m])[:, None]
+        r = 5.0
+        Y = rng.negative_binomial(r, r / (r + mu)).astype(np.float32)
+        Y[:, n_genes - n_rare:] = 0
+        for g in range(n_genes - n_rare, n_genes):
+            Y[rng.choice(int(n), 3, replace=False), g] = 1
+        if t == 0:
+            Y[:, n_genes - n_rare - 1] = 0
+        Y[rng.integers(int(n))] = 0
+        Xs.append(Y); locs.append(xy); tps.append(np.full(int(n), t))
+    data = SpatialData(np.concatenate(Xs), np.concatenate(tps), np.concatenate(locs))
+    data.var_names = np.array([f"g{g:04d}" for g in range(n_genes)])
+    data.uns = {"module": module}
+    return data
