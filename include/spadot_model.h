@@ -622,6 +622,33 @@ int spadot_pre_scale_write(const long long *indptr, const int *cidx, const float
                            const int *colpos, const double *total, double target, const double *mean, const double *stdv,
                            double clip, int nrows, float *out, void *stream);
 
+/* ---------------------------------------------------------------- SCTransform (csrc/sctransform.hip)
+ * The per-gene work of SpaDOT/utils/sctransform (vst with method='poisson', theta.ml, Pearson residuals) on one time point t,
+ * counts in the CSC layout above.  The N spots t keeps (non-zero total) are given as lu[k] (log10 total, row order), krow[k]
+ * (their rows), and per row lur[r] (log10 total, 0 elsewhere) and rowmap[r] (k, or -1).  One wavefront per gene, fp64 sums in
+ * a fixed order (bitwise repeatable).  pars[i] = (theta, b0, b1).
+ *
+ * sct_gene_stats:  out[i, 3] = sum log1p(y), sum y, sum (y - mean)^2 over the N spots, gene genes[i]
+ * sct_fit:         per step-1 gene: Poisson IRLS of y ~ 1 + log_umi (tol, maxit), then theta.ml (limit, eps) on the fitted
+ *                  mu of the last iteration; out[i, 8] = theta, b0, b1, fitted b0, fitted b1, iterations, theta iterations,
+ *                  sum y
+ * sct_resid_stats: r = (y - mu) / sqrt(mu + mu^2 / theta), mu = exp(b0 + b1 x); out[i, 3] = mean, variance (ddof 1) of
+ *                  clip(r, +-clip_hi), mean of clip(r, +-clip_lo)
+ * sct_resid_write: out[i * N + k] = clip(r, +-clip_lo) - center[i], fp64 dense
+ * sct_polygamma:   psi[i], psi1[i] = digamma, trigamma of x[i] (the device functions sct_fit uses) */
+int spadot_sct_gene_stats(const long long *colptr, const int *ridx, const float *val, const int *tp_off, int t, int Gk,
+                          const int *genes, int N, double *out, void *stream);
+int spadot_sct_fit(const long long *colptr, const int *ridx, const float *val, const int *tp_off, int t, int G1,
+                   const int *genes, const double *lur, const double *lu, int N, double tol, int maxit, int limit, double eps,
+                   double *out, void *stream);
+int spadot_sct_resid_stats(const long long *colptr, const int *ridx, const float *val, const int *tp_off, int t, int Gk,
+                           const int *genes, const double *lur, const double *lu, int N, const double *pars, double clip_hi,
+                           double clip_lo, double *out, void *stream);
+int spadot_sct_resid_write(const long long *colptr, const int *ridx, const float *val, const int *tp_off, int t, int S,
+                           const int *genes, const double *lur, const double *lu, const int *krow, const int *rowmap, int N,
+                           const double *pars, const double *center, double clip_lo, double *out, void *stream);
+int spadot_sct_polygamma(const double *x, int n, double *psi, double *psi1, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 """spadot_amd -- MI355X-native implementation of SpaDOT's preprocess, train and analyze stages.
 
 `preprocess` mirrors SpaDOT.preprocess (SPARK-X gene selection and scaling on the device; the gene clusters of the balancing
-rule come from K-means in place of SCTransform + Louvain), `train` mirrors SpaDOT.train and `analyze` mirrors
+rule come from K-means by default, or with gene_clusters='louvain' from the reference's SCTransform + Louvain), `train` mirrors SpaDOT.train and `analyze` mirrors
 SpaDOT.analyze (reference SpaDOT/__init__.py:1-5); `python -m spadot_amd preprocess|train|analyze` is the command line
 (reference cli.py).  Importing this package does not load the HIP libraries; the first numeric call does, and fails loudly
 if they have not been built (python -m spadot_amd.csrc.build)."""

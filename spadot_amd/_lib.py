@@ -265,6 +265,11 @@ def model_lib():
         "spadot_sparkx_pvals": [vp, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp],
         "spadot_pre_lognorm_stats": [vp, vp, vp, vp, ci, ci, vp, vp, cd, vp, vp, vp],
         "spadot_pre_scale_write": [vp, vp, vp, vp, ci, ci, vp, vp, cd, vp, vp, cd, ci, vp, vp],
+        "spadot_sct_gene_stats": [vp, vp, vp, vp, ci, ci, vp, ci, vp, vp],
+        "spadot_sct_fit": [vp, vp, vp, vp, ci, ci, vp, vp, vp, ci, cd, ci, ci, cd, vp, vp],
+        "spadot_sct_resid_stats": [vp, vp, vp, vp, ci, ci, vp, vp, vp, ci, vp, cd, cd, vp, vp],
+        "spadot_sct_resid_write": [vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, cd, vp, vp],
+        "spadot_sct_polygamma": [vp, ci, vp, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)

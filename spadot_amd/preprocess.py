@@ -2,7 +2,7 @@
 (SpaDOT/utils/_utils.py:121-414) on the MI355X.
 
     preprocess(args)   args: data, output_dir (default: the data's directory), prefix ('preprocessed_'),
-                       feature_selection (True), device ('cuda:0')
+                       feature_selection (True), device ('cuda:0'), gene_clusters ('kmeans' or 'louvain'; default 'kmeans')
 
 Per time point (in order of first appearance) with feature selection on: the SCTransform gene filter (a count >= 0.01 in at
 least 5 spots), the spot and gene filters of _sparkx, the 11 SPARK-X statistics and p-values per gene, ACAT, Benjamini-
@@ -13,13 +13,14 @@ over those genes, log1p, scale (ddof 1, std 0 -> 1, no clip), float32.  The per-
 (row permutation, CSR -> CSC, the N x 22 kernel coordinates, ordering G values).
 
 Deviations from the reference:
-  * the `cluster` column of {tp}_SVG_sparkx_clustered_louvain.csv comes from K-means, not Louvain: the genes' standardised
+  * by default the `cluster` column of {tp}_SVG_sparkx_clustered_louvain.csv comes from K-means, not Louvain: the genes' standardised
     log1p(x * 1e4 / total) over the time point's spots, clipped at +-sqrt(N/30), its 29 leading principal components of genes
     as points (the device K-means admits 29 dimensions at k = 10; the reference's graph uses 30),
     KMeansDevice(10, random_state=1993, n_init=10).  The reference clusters SCTransform Pearson residuals with a 100-NN graph
-    and Louvain at rising resolution until >= 10 clusters; neither SCTransform nor louvain is available.  Only
-    the per-cluster quota of the balancing rule reads the clusters, so the choice of genes beyond the smallest time point's
-    list can differ from the reference's;
+    and Louvain at rising resolution until >= 10 clusters; gene_clusters='louvain' does that (cluster_genes_louvain on the
+    device SCTransform of spadot_amd.sctransform; its own deviations are listed there and in DESIGN 7c).  Only the
+    per-cluster quota of the balancing rule reads the clusters, so with K-means the choice of genes beyond the smallest time
+    point's list can differ from the reference's;
   * p-values use the exact survival function of ylam (l1 chi^2_1 + l2 chi^2_1) in place of Davies / Liu (Liu is exact too
     when l1 = l2, which is SPARK-X's case up to rounding), and a gene with ylam = 0 gets p = 1 (the reference gets NaN and
     ACAT raises);
@@ -32,6 +33,7 @@ import numpy as np
 import torch
 
 from ._lib import model_lib
+from .sctransform import sctransform
 from .utils._preprocess_utils import (N_KERNELS, RawCounts, by_adjust, kernel_coordinates, load_counts, rank_genes,  # noqa: F401
                                       select_svgs, timepoint_order)
 
@@ -41,6 +43,9 @@ TARGET_SUM = 1e-4              # _preprocess_utils.py:33 (sic)
 CLUSTER_TARGET = 1e4           # the clustering input's normalisation
 N_PCS = 29                     # scanpy's n_pcs=30 less one: (10 + 256) * d <= 7936 doubles of LDS caps the device K-means at d = 29
 N_GENE_CLUSTERS = 10
+N_PCS_LOUVAIN = 30             # sc.pp.neighbors(n_pcs=30)
+N_NEIGHBORS = 100              # sc.pp.neighbors(n_neighbors=100)
+GENE_CLUSTERS = ("kmeans", "louvain")
 PVAL_NODES = 256               # trapezoid nodes of the two-term survival function
 CSV_SUFFIX = "_SVG_sparkx_clustered_louvain.csv"
 
@@ -242,6 +247,34 @@ def cluster_genes(dc, t, genes, total, k=N_GENE_CLUSTERS, n_pcs=N_PCS):
     return np.asarray(km.labels_, dtype=np.int64)
 
 
+def _pca_scores(M, npc):
+    """The npc leading principal-component scores of the rows of M (fp64, centred per column here) from an eigendecomposition
+    of the smaller Gram matrix, rows x rows or columns x columns (deterministic, no random draws)."""
+    M = M - M.mean(0, keepdim=True)
+    if M.shape[0] <= M.shape[1]:
+        w, V = torch.linalg.eigh(M @ M.T)                  # ascending eigenvalues; scores = V sqrt(w)
+        w, V = w.flip(0)[:npc], V.flip(1)[:, :npc]
+        return V * w.clamp(min=0).sqrt()[None, :]
+    w, U = torch.linalg.eigh(M.T @ M)                      # column-side vectors; scores = M U
+    return M @ U.flip(1)[:, :npc]
+
+
+def cluster_genes_louvain(dc, t, genes, sct, k=N_GENE_CLUSTERS, n_pcs=N_PCS_LOUVAIN, n_neighbors=N_NEIGHBORS):
+    """_cluster_SVGs (SpaDOT/utils/_utils.py:195-221) on the genes `genes` (column indices) of time point t: their SCTransform
+    scale.data rows (sct: the time point's SCTResult), the 30 leading principal components of genes as points, the
+    Gaussian 100-NN graph and Louvain at resolution 1.0, + 0.1, ... until >= k communities.  Returns int64 labels (0 = the
+    largest community)."""
+    from .utils._sctransform_utils import cluster_by_resolution, gauss_knn_graph
+    genes = np.asarray(genes)
+    if genes.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    M = sct.scale_data(genes)                                                      # [S, N] fp64 on the device
+    pcs = _pca_scores(M, min(n_pcs, genes.size, M.shape[1]))
+    W = gauss_knn_graph(pcs, n_neighbors)
+    labels, _ = cluster_by_resolution(W, k)
+    return labels
+
+
 def scale_output(dc, cols):
     """Step 4 on the columns `cols`: per time point normalize_total(target_sum=1e-4) over those columns, log1p, scale."""
     mask = np.zeros((dc.T, dc.G), dtype=bool)
@@ -251,11 +284,15 @@ def scale_output(dc, cols):
     return dc.scale_write(cols, total, TARGET_SUM, mean, std)
 
 
-def preprocess_counts(raw, feature_selection=True, device="cuda:0", output_dir=None, cluster=True):
+def preprocess_counts(raw, feature_selection=True, device="cuda:0", output_dir=None, cluster=True, gene_clusters="kmeans"):
     """The whole stage on a RawCounts.  Returns a dict: X (float32 [n, S] numpy), genes, cols (column indices), timepoint,
     spatial, perm (input row of each output row), counts (scipy CSR of the raw counts of `cols`), tps, and with feature
     selection the per-time-point SPARK-X results `sparkx` and SVG tables `tables` (genes, combinedPval, adjustedPval,
-    cluster).  Writes the per-time-point CSVs and SVG_genes.txt into output_dir when given."""
+    cluster).  gene_clusters: 'kmeans' (cluster_genes, the default) or 'louvain' (SCTransform of each time point, then
+    cluster_genes_louvain; the SCTResults are returned as `sct`).  Writes the per-time-point CSVs and SVG_genes.txt into
+    output_dir when given."""
+    if gene_clusters not in GENE_CLUSTERS:
+        raise ValueError(f"gene_clusters must be one of {GENE_CLUSTERS}, not {gene_clusters!r}")
     dc = DeviceCounts(raw, device)
     out = dict(tps=dc.tps, timepoint=dc.timepoint, spatial=dc.spatial, perm=dc.perm)
     if feature_selection:
@@ -265,7 +302,14 @@ def preprocess_counts(raw, feature_selection=True, device="cuda:0", output_dir=N
             order, n_keep = rank_genes(r["adjusted"], r["combined"])
             sel = order[:n_keep]
             cols = r["genes"][sel]
-            clus = cluster_genes(dc, t, cols, r["total"]) if cluster else np.zeros(cols.size, dtype=np.int64)
+            if not cluster:
+                clus = np.zeros(cols.size, dtype=np.int64)
+            elif gene_clusters == "louvain":
+                sct = sctransform(dc, t)
+                clus = cluster_genes_louvain(dc, t, cols, sct)
+                r["sct"] = sct
+            else:
+                clus = cluster_genes(dc, t, cols, r["total"])
             r.update(selected=cols, cluster=clus)
             tables.append((dc.genes[cols], r["combined"][sel], r["adjusted"][sel], clus))
             if output_dir:
@@ -314,7 +358,8 @@ def preprocess(args):
     prefix = "" if prefix is None else prefix
     device = getattr(args, "device", None) or "cuda:0"
     fs = bool(getattr(args, "feature_selection", True))
-    res = preprocess_counts(raw, feature_selection=fs, device=device, output_dir=args.output_dir)
+    gc = getattr(args, "gene_clusters", None) or "kmeans"
+    res = preprocess_counts(raw, feature_selection=fs, device=device, output_dir=args.output_dir, gene_clusters=gc)
     stem = os.path.splitext(os.path.basename(path))[0] if path else "data"
     c = res["counts"]
     np.savez(os.path.join(args.output_dir, prefix + stem + ".npz"), X=res["X"], timepoint=res["timepoint"],
