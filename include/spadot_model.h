@@ -302,32 +302,21 @@ int spadot_sum_parts(const double *part, int n, double scale, float *out, void *
  * Launched at the head and the end of a captured stage it dates the stage on the GPU with no profiler attached. */
 int spadot_stamp(unsigned long long *buf, int slot, void *stream);
 
-/* One Lloyd iteration of K-means for R restarts at once (fp64, no atomics: two fits of the same data are bitwise
- * identical).  X [n, D] (centred data), C [R, K, D] centres (updated in place unless done[r]), part: work space of
- * R * ceil(n/256) * (K*(D+1) + 1) doubles, done [R] int flags (set when the squared centre shift <= tol), inertia [R]
- * = inertia of the centres the iteration started from, labels [R, n] int32 or NULL.  update = 0: assignment, partial
- * sums and labels only.  K <= 32, D <= 32.  (KMeans of _train_utils.py:255-269.) */
-int spadot_lloyd_step(const double *X, double *C, int n, int D, int K, int R, double tol, double *part, int *done,
-                      double *inertia, int *labels, int update, void *stream);
-/* The same iteration for SEVERAL data sets in one launch pair (the per-epoch K-means of all time points,
- * _train_utils.py:255-269): group g owns rows xoff[g] .. xoff[g] + npts[g] - 1 of X [sum npts, D] and the restarts
- * g * rpg .. (g + 1) * rpg - 1 of C [groups * rpg, K, D]; tol[g] is its stopping threshold (device arrays); n_max = the largest
- * npts (grid size); part needs groups * rpg * ceil(n_max / 256) * (K (D + 1) + 1) doubles.  skip_done != 0: restarts whose
- * done flag is set are left alone entirely (their centres are final; inertia[r] then still belongs to the centres of the
- * iteration that froze them -- measure the final one with a call that has skip_done = 0 and every done flag set). */
-int spadot_lloyd_step_groups(const double *X, double *C, const int *xoff, const int *npts, int n_max, int groups, int rpg, int D,
-                             int K, const double *tol, double *part, int *done, double *inertia, int update, int skip_done,
-                             void *stream);
-
-/* The same iteration with a cluster count PER RESTART (the analyze stage's k = 4 .. 20 sweep, all data sets and all k in one
- * launch pair): restart r belongs to group rgroup[r] (rows xoff[g] .. xoff[g] + npts[g] - 1 of X, stopping threshold tol[g])
- * and has Kr[r] <= K_max clusters; C [R, K_max, D] keeps its first Kr[r] rows (the rest is padding, never read or written);
- * part needs R * ceil(n_max / 256) * (K_max (D + 1) + 1) doubles.  A restart with Kr[r] == K_max sums in the order of
- * spadot_lloyd_step_groups, bit for bit.  update / skip_done as there.  rgroup, Kr: int32 device arrays [R]. */
-int spadot_lloyd_step_sweep(const double *X, double *C, const int *xoff, const int *npts, int n_max, int R, const int *rgroup,
-                            const int *Kr, int K_max, int D, const double *tol, double *part, int *done, double *inertia, int update,
-                            int skip_done, void *stream);
-/* k-means++ seeding (sklearn's rule as in spadot_amd.kmeans.KMeansDevice: 2 + int(log k) candidates per further centre, drawn
+/* One Lloyd iteration of K-means for R restarts at once, over several data sets and cluster counts in one launch pair (fp64,
+ * no atomics: two fits of the same data are bitwise identical).  Restart r belongs to set rgroup[r] (rows xoff[g] .. xoff[g] +
+ * npts[g] - 1 of the centred data X [sum npts, D], stopping threshold tol[g]) and has Kr[r] <= K_max clusters; C [R, K_max, D]
+ * keeps its first Kr[r] rows, updated in place unless done[r] (the rest is padding, never read or written).  Each restart sums
+ * over its own clusters and points only, so its result does not depend on the other restarts of the launch.  done [R] int
+ * flags (set when the squared centre shift <= tol[g]), inertia [R] = inertia of the centres the iteration started from.  n_max
+ * = the largest npts (grid size); part: work space of R * ceil(n_max / 256) * (K_max (D + 1) + 1) doubles.  skip_done != 0:
+ * restarts whose done flag is set are left alone entirely (their centres are final; inertia[r] then still belongs to the
+ * centres of the iteration that froze them -- measure the final one with a call that has skip_done = 0 and every done flag
+ * set).  xoff, npts: int32 device arrays [sets]; rgroup, Kr: int32 device arrays [R]; tol: fp64 device array [sets].
+ * K_max <= 32, D <= 32, (K_max + 256) * D <= 7936.  (KMeans of _train_utils.py:255-269 and _analyze_utils.py:42-105.) */
+int spadot_lloyd_step(const double *X, double *C, const int *xoff, const int *npts, int n_max, int R, const int *rgroup,
+                      const int *Kr, int K_max, int D, const double *tol, double *part, int *done, double *inertia, int skip_done,
+                      void *stream);
+/* k-means++ seeding (sklearn's rule: 2 + int(log k) candidates per further centre, drawn
  * by potential; the candidate whose new potential is smallest wins, first on ties) for P problems in one launch, one workgroup
  * each.  Problem p seeds pK[p] <= K_max centres on group pset[p] (rows xoff[g] .. xoff[g] + npts[g] - 1 of the centred data
  * X, npts[g] <= n_max), starting from row pfirst[p]; round c (1 <= c < pK[p]) reads its uniforms from

@@ -244,9 +244,7 @@ def model_lib():
         "spadot_sqerr_backward": [vp, vp, vp, ll, cd, ci, vp, vp],
         "spadot_kmeans_assign": [vp, vp, ci, ci, ci, ci, vp, vp],
         "spadot_sgemm_small": [ci, vp, ci, vp, ci, vp, ci, ci, ci, ci, vp, ci, ll, ll, ll, vp],
-        "spadot_lloyd_step": [vp, vp, ci, ci, ci, ci, cd, vp, vp, vp, vp, ci, vp],
-        "spadot_lloyd_step_groups": [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, ci, vp],
-        "spadot_lloyd_step_sweep": [vp, vp, vp, vp, ci, ci, vp, vp, ci, ci, vp, vp, vp, vp, ci, ci, vp],
+        "spadot_lloyd_step": [vp, vp, vp, vp, ci, ci, vp, vp, ci, ci, vp, vp, vp, vp, ci, vp],
         "spadot_kmeanspp_seed": [vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp],
         "spadot_colsum": [vp, ci, ci, vp, vp],
         "spadot_cast_rows_multi": [vp, vp, vp, vp, vp, ci, vp],

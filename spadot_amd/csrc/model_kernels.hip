@@ -1178,23 +1178,19 @@ __global__ void k_stamp(unsigned long long *buf, int slot) {
 }
 
 // ------------------------------------------------------------------------------------------
-// Lloyd iterations of K-means for R restarts at once (fp64, deterministic: no atomics).
+// Lloyd iterations of K-means for R restarts at once (fp64, deterministic: no atomics).  Restart r belongs to data set
+// rgrp[r] (rows xoff[g] .. xoff[g] + npts[g] - 1 of X) and has its own cluster count Kr[r] <= K; K is the padding of
+// C [R, K, D] and of the partial-sum slots, and the grid is sized by the largest set (chunks past a set's end return at once).
 //   k_lloyd_assign: block = (restart r, chunk of 256 points): nearest centre per point (first minimum wins),
 //                   per-block cluster sums / counts / inertia in a fixed order -> part[r][chunk][K*(D+1) + 1]
 //   k_lloyd_update: block = restart: partials summed in chunk order, centres moved (empty cluster: kept), squared
-//                   shift compared with tol, `done` restarts frozen.
+//                   shift compared with tol[g], `done` restarts frozen.
+// Each restart loops over its own Kr[r] clusters only, so its arithmetic does not depend on the other restarts of the launch.
 // ------------------------------------------------------------------------------------------
 constexpr int LL_PTS = 256, LL_MAXK = 32, LL_MAXD = 32;
-// Groups (several data sets in one launch: the per-epoch K-means of ALL time points, _train_utils.py:255-269): restart r
-// belongs to group r / rpg, whose points are rows xoff[g] .. xoff[g] + npts[g] - 1 of X; n is then the LARGEST group (grid
-// and label stride); chunks past a group's end return at once.  xoff == nullptr: one data set of n rows, as before.
-// Sweep (the analyze stage's k = 4 .. 20 sweep, spadot_lloyd_step_sweep): Kr [R] gives restart r its own cluster count Kr[r]
-// <= K (K is then K_max, the padding of C [R, K_max, D] and of the partial-sum slots) and rgrp [R] its group; each restart
-// loops over its own Kr[r] only, so for Kr[r] == K the summation order is the uniform one.  Kr == rgrp == nullptr: as before.
 __global__ __launch_bounds__(LL_PTS) void k_lloyd_assign(const double *__restrict__ X, const double *__restrict__ C,
-                                                         int n, int D, int K, double *__restrict__ part,
-                                                         int *__restrict__ labels /* [R, n] or null */,
-                                                         const int *__restrict__ xoff, const int *__restrict__ npts, int rpg,
+                                                         int D, int K, double *__restrict__ part,
+                                                         const int *__restrict__ xoff, const int *__restrict__ npts,
                                                          const int *__restrict__ skip_done,
                                                          const int *__restrict__ Kr, const int *__restrict__ rgrp) {
     extern __shared__ double ll_dyn[];           // K*D centres, then 256*D point coordinates
@@ -1204,15 +1200,11 @@ __global__ __launch_bounds__(LL_PTS) void k_lloyd_assign(const double *__restric
     const int r = blockIdx.y, chunk = blockIdx.x, t = threadIdx.x;
     const int i = chunk * LL_PTS + t;
     const int nchunk = gridDim.x;
-    const int stride_n = n;
     if (skip_done != nullptr && skip_done[r] != 0) return;      // a restart that has converged: nothing reads its partials again
-    if (xoff != nullptr) {
-        const int g = rgrp != nullptr ? rgrp[r] : r / rpg;
-        n = npts[g];
-        X += (size_t)xoff[g] * D;
-        if (chunk * LL_PTS >= n) return;        // (uniform for the workgroup)
-    }
-    const int Kl = Kr != nullptr ? min(Kr[r], K) : K;  // this restart's cluster count; K is the padded stride
+    const int g = rgrp[r], n = npts[g];
+    X += (size_t)xoff[g] * D;
+    if (chunk * LL_PTS >= n) return;            // (uniform for the workgroup)
+    const int Kl = min(Kr[r], K);               // this restart's cluster count; K is the padded stride
     for (int e = t; e < Kl * D; e += LL_PTS) s_c[e] = C[(size_t)r * K * D + e];
     const int rows = min(LL_PTS, n - chunk * LL_PTS);
 #pragma unroll 4
@@ -1227,7 +1219,6 @@ __global__ __launch_bounds__(LL_PTS) void k_lloyd_assign(const double *__restric
             for (int c = 0; c < D; c++) { const double df = s_x[t * D + c] - s_c[k * D + c]; d2 += df * df; }
             if (d2 < best) { best = d2; arg = k; }
         }
-        if (labels) labels[(size_t)r * stride_n + i] = arg;
     }
     s_lab[t] = arg;
     const double inertia = block_sum_d(i < n ? best : 0.0, s_red);       // (includes the barrier after s_lab)
@@ -1245,9 +1236,9 @@ __global__ __launch_bounds__(LL_PTS) void k_lloyd_assign(const double *__restric
     if (t == 0) out[(size_t)K * (D + 1)] = inertia;
 }
 
-__global__ __launch_bounds__(256) void k_lloyd_update(const double *__restrict__ part, int nchunk, int D, int K,
-                                                      double tol, double *__restrict__ C, int *__restrict__ done,
-                                                      double *__restrict__ inertia, const int *__restrict__ npts, int rpg,
+__global__ __launch_bounds__(256) void k_lloyd_update(const double *__restrict__ part, int slots, int D, int K,
+                                                      double *__restrict__ C, int *__restrict__ done,
+                                                      double *__restrict__ inertia, const int *__restrict__ npts,
                                                       const double *__restrict__ tolv, int skip_done,
                                                       const int *__restrict__ Kr, const int *__restrict__ rgrp) {
     __shared__ double s_new[LL_MAXK * (LL_MAXD + 1)];
@@ -1255,13 +1246,10 @@ __global__ __launch_bounds__(256) void k_lloyd_update(const double *__restrict__
     const int r = blockIdx.x, t = threadIdx.x;
     if (skip_done && done[r] != 0) return;       // frozen: centres and inertia stay (the caller measures the final inertia with skip_done = 0)
     const size_t stride = (size_t)K * (D + 1) + 1;
-    const int slots = nchunk;                    // partial slots per restart (the largest group's chunk count)
-    if (npts != nullptr) {
-        const int g = rgrp != nullptr ? rgrp[r] : r / rpg;
-        nchunk = (npts[g] + LL_PTS - 1) / LL_PTS;
-        tol = tolv[g];
-    }
-    const int Kl = Kr != nullptr ? min(Kr[r], K) : K;
+    const int g = rgrp[r];
+    const int nchunk = (npts[g] + LL_PTS - 1) / LL_PTS;     // this set's chunks of the `slots` per restart
+    const double tol = tolv[g];
+    const int Kl = min(Kr[r], K);
     for (int pq = t; pq < Kl * (D + 1); pq += 256) {
         double acc = 0.0;
         for (int ch = 0; ch < nchunk; ch++) acc += part[((size_t)r * slots + ch) * stride + pq];
@@ -1288,9 +1276,10 @@ __global__ __launch_bounds__(256) void k_lloyd_update(const double *__restrict__
 }
 
 // ------------------------------------------------------------------------------------------
-// k-means++ seeding for many problems in one launch (the analyze stage's sweep: every (data set, k, restart) triple is a
-// problem).  Block = problem p: the k - 1 selection rounds of KMeansDevice._init_centers (sklearn's rule: 2 + int(log k)
-// candidates drawn by potential, the one with the smallest new potential wins, first minimum on ties).  closest [n] lives
+// k-means++ seeding for many problems in one launch (every (data set, k, restart) triple of a plan of spadot_amd.kmeans is a
+// problem).  Block = problem p: the k - 1 selection rounds of sklearn's k-means++ rule (2 + int(log k) candidates drawn by
+// potential, the one with the smallest new potential wins, first minimum on ties; the torch rounds of kmeans._Plan state
+// the same rule for small plans).  closest [n] lives
 // in a global work space row (it outgrows LDS at 50 000 points).  Per round:
 //   1. thread t owns the contiguous segment [t*seg, (t+1)*seg) of closest: its segment total, then a fixed-order
 //      (Hillis-Steele) scan of the 256 totals gives each segment's base;
@@ -2832,54 +2821,19 @@ int spadot_knn(const double *x, int n, int d, int kk, int *out, void *stream) {
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
-int spadot_lloyd_step(const double *X, double *C, int n, int D, int K, int R, double tol, double *part, int *done,
-                      double *inertia, int *labels, int update, void *stream) {
-    if (n <= 0 || D <= 0 || D > LL_MAXD || K <= 0 || K > LL_MAXK || R <= 0 || R > 65535 || !part) return -22;
-    if ((size_t)K * D + (size_t)LL_PTS * D > 7936) return -22;     // dynamic LDS stays under 62 KB
-    hipStream_t st_ = (hipStream_t)stream;
-    const int nchunk = (n + LL_PTS - 1) / LL_PTS;
-    const size_t lds = sizeof(double) * ((size_t)K * D + (size_t)LL_PTS * D);      // <= 8 KB + 64 KB
-    hipLaunchKernelGGL(k_lloyd_assign, dim3(nchunk, R), dim3(LL_PTS), lds, st_, X, (const double *)C, n, D, K, part, labels,
-                       (const int *)nullptr, (const int *)nullptr, 1, (const int *)nullptr, (const int *)nullptr, (const int *)nullptr);
-    if (update)
-        hipLaunchKernelGGL(k_lloyd_update, dim3(R), dim3(256), 0, st_, (const double *)part, nchunk, D, K, tol, C, done, inertia,
-                           (const int *)nullptr, 1, (const double *)nullptr, 0, (const int *)nullptr, (const int *)nullptr);
-    return hipGetLastError() == hipSuccess ? 0 : -5;
-}
-
-int spadot_lloyd_step_groups(const double *X, double *C, const int *xoff, const int *npts, int n_max, int groups, int rpg, int D,
-                             int K, const double *tol, double *part, int *done, double *inertia, int update, int skip_done,
-                             void *stream) {
-    if (n_max <= 0 || groups <= 0 || rpg <= 0 || D <= 0 || D > LL_MAXD || K <= 0 || K > LL_MAXK || (long long)groups * rpg > 65535)
-        return -22;
-    if (!X || !C || !xoff || !npts || !tol || !part || !done || !inertia) return -22;
-    if ((size_t)K * D + (size_t)LL_PTS * D > 7936) return -22;
-    hipStream_t st_ = (hipStream_t)stream;
-    const int nchunk = (n_max + LL_PTS - 1) / LL_PTS, R = groups * rpg;
-    const size_t lds = sizeof(double) * ((size_t)K * D + (size_t)LL_PTS * D);
-    hipLaunchKernelGGL(k_lloyd_assign, dim3(nchunk, R), dim3(LL_PTS), lds, st_, X, (const double *)C, n_max, D, K, part,
-                       (int *)nullptr, xoff, npts, rpg, skip_done ? (const int *)done : (const int *)nullptr, (const int *)nullptr,
-                       (const int *)nullptr);
-    if (update)
-        hipLaunchKernelGGL(k_lloyd_update, dim3(R), dim3(256), 0, st_, (const double *)part, nchunk, D, K, 0.0, C, done, inertia,
-                           npts, rpg, tol, skip_done, (const int *)nullptr, (const int *)nullptr);
-    return hipGetLastError() == hipSuccess ? 0 : -5;
-}
-
-int spadot_lloyd_step_sweep(const double *X, double *C, const int *xoff, const int *npts, int n_max, int R, const int *rgroup,
-                            const int *Kr, int K_max, int D, const double *tol, double *part, int *done, double *inertia, int update,
-                            int skip_done, void *stream) {
+int spadot_lloyd_step(const double *X, double *C, const int *xoff, const int *npts, int n_max, int R, const int *rgroup,
+                      const int *Kr, int K_max, int D, const double *tol, double *part, int *done, double *inertia, int skip_done,
+                      void *stream) {
     if (n_max <= 0 || R <= 0 || R > 65535 || D <= 0 || D > LL_MAXD || K_max <= 0 || K_max > LL_MAXK) return -22;
     if (!X || !C || !xoff || !npts || !rgroup || !Kr || !tol || !part || !done || !inertia) return -22;
-    if ((size_t)K_max * D + (size_t)LL_PTS * D > 7936) return -22;
+    if ((size_t)K_max * D + (size_t)LL_PTS * D > 7936) return -22;     // dynamic LDS stays under 62 KB
     hipStream_t st_ = (hipStream_t)stream;
     const int nchunk = (n_max + LL_PTS - 1) / LL_PTS;
-    const size_t lds = sizeof(double) * ((size_t)K_max * D + (size_t)LL_PTS * D);
-    hipLaunchKernelGGL(k_lloyd_assign, dim3(nchunk, R), dim3(LL_PTS), lds, st_, X, (const double *)C, n_max, D, K_max, part,
-                       (int *)nullptr, xoff, npts, 1, skip_done ? (const int *)done : (const int *)nullptr, Kr, rgroup);
-    if (update)
-        hipLaunchKernelGGL(k_lloyd_update, dim3(R), dim3(256), 0, st_, (const double *)part, nchunk, D, K_max, 0.0, C, done,
-                           inertia, npts, 1, tol, skip_done, Kr, rgroup);
+    const size_t lds = sizeof(double) * ((size_t)K_max * D + (size_t)LL_PTS * D);      // <= 8 KB + 64 KB
+    hipLaunchKernelGGL(k_lloyd_assign, dim3(nchunk, R), dim3(LL_PTS), lds, st_, X, (const double *)C, D, K_max, part, xoff, npts,
+                       skip_done ? (const int *)done : (const int *)nullptr, Kr, rgroup);
+    hipLaunchKernelGGL(k_lloyd_update, dim3(R), dim3(256), 0, st_, (const double *)part, nchunk, D, K_max, C, done, inertia, npts,
+                       tol, skip_done, Kr, rgroup);
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

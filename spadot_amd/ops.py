@@ -1837,52 +1837,29 @@ def kmeans_assign(x, centers):
 
 # ----------------------------------------------------------------------------- optimiser
 
-def lloyd_steps(X, C, tol, done, inertia, part, steps):
-    """`steps` Lloyd iterations for all restarts (include/spadot_model.h: spadot_lloyd_step); X [n, D], C [R, K, D]
-    fp64 device tensors, C / done / inertia updated in place."""
-    n, D = X.shape
-    R, K, _ = C.shape
-    lib = model_lib()
-    for _ in range(steps):
-        _check(lib.spadot_lloyd_step(_p(X), _p(C), n, D, K, R, float(tol), _p(part), _p(done), _p(inertia), None, 1,
-                                     _stream()), "spadot_lloyd_step")
-
-
-def lloyd_steps_groups(X, C, xoff, npts, n_max, groups, rpg, tol, done, inertia, part, steps, update=True, skip_done=False):
-    """`steps` Lloyd iterations for several data sets at once (spadot_lloyd_step_groups): X [sum n, D] fp64, C [groups * rpg, K,
-    D], xoff / npts int32 [groups], tol fp64 [groups] device tensors; C / done / inertia updated in place."""
-    D = X.shape[1]
-    K = C.shape[1]
-    lib = model_lib()
-    for _ in range(steps):
-        _check(lib.spadot_lloyd_step_groups(_p(X), _p(C), _p(xoff), _p(npts), int(n_max), int(groups), int(rpg), D, K, _p(tol),
-                                            _p(part), _p(done), _p(inertia), 1 if update else 0, 1 if skip_done else 0, _stream()),
-               "spadot_lloyd_step_groups")
-
-
-def lloyd_steps_sweep(X, C, xoff, npts, n_max, rgroup, Kr, tol, done, inertia, part, steps, update=True, skip_done=False):
-    """`steps` Lloyd iterations with a cluster count per restart (spadot_lloyd_step_sweep): X [sum n, D] fp64, C [R, K_max, D]
-    fp64, xoff / npts int32 [groups], rgroup / Kr int32 [R], tol fp64 [groups] device tensors; C / done / inertia updated in
-    place."""
+def lloyd_steps(X, C, xoff, npts, n_max, rgroup, Kr, tol, done, inertia, part, steps, skip_done=False):
+    """`steps` Lloyd iterations with a data set and a cluster count per restart (include/spadot_model.h: spadot_lloyd_step):
+    X [sum n, D] fp64, C [R, K_max, D] fp64, xoff / npts int32 [sets], rgroup / Kr int32 [R], tol fp64 [sets] device tensors;
+    C / done / inertia updated in place."""
     D = X.shape[1]
     R, K_max = C.shape[0], C.shape[1]
     lib = model_lib()
     for _ in range(steps):
-        _check(lib.spadot_lloyd_step_sweep(_p(X), _p(C), _p(xoff), _p(npts), int(n_max), R, _p(rgroup), _p(Kr), K_max, D, _p(tol),
-                                           _p(part), _p(done), _p(inertia), 1 if update else 0, 1 if skip_done else 0, _stream()),
-               "spadot_lloyd_step_sweep")
+        _check(lib.spadot_lloyd_step(_p(X), _p(C), _p(xoff), _p(npts), int(n_max), R, _p(rgroup), _p(Kr), K_max, D, _p(tol),
+                                     _p(part), _p(done), _p(inertia), 1 if skip_done else 0, _stream()), "spadot_lloyd_step")
 
 
-def kmeanspp_seed(X, xoff, npts, n_max, pset, pK, pfirst, puoff, U, K_max):
+def kmeanspp_seed(X, xoff, npts, n_max, pset, pK, pfirst, puoff, U, K_max, out=None):
     """k-means++ seeding of P problems in one launch (spadot_kmeanspp_seed).  X [sum n, D] centred fp64, xoff / npts int32
     [groups]; per problem int32 [P]: set, k, first-centre row, offset into the fp64 uniforms U.  Returns (idx [P, K_max] int32,
-    centers [P, K_max, D] fp64), padding rows -1 / 0."""
+    centers [P, K_max, D] fp64), padding rows -1 / 0.  out: (idx, centers, closest [P, n_max] fp64) to write into instead of
+    new tensors."""
     _need_cuda(X)
     P, D = int(pset.shape[0]), int(X.shape[1])
     dev = X.device
-    idx = torch.empty((P, K_max), dtype=torch.int32, device=dev)
-    centers = torch.empty((P, K_max, D), dtype=torch.float64, device=dev)
-    closest = torch.empty((P, int(n_max)), dtype=torch.float64, device=dev)
+    idx, centers, closest = out if out is not None else (
+        torch.empty((P, K_max), dtype=torch.int32, device=dev), torch.empty((P, K_max, D), dtype=torch.float64, device=dev),
+        torch.empty((P, int(n_max)), dtype=torch.float64, device=dev))
     _check(model_lib().spadot_kmeanspp_seed(_p(X), _p(xoff), _p(npts), D, P, _p(pset), _p(pK), _p(pfirst), _p(puoff), _p(U),
                                             int(K_max), int(n_max), _p(closest), _p(idx), _p(centers), _stream()),
            "spadot_kmeanspp_seed")

@@ -232,16 +232,7 @@ def cluster_genes(dc, t, genes, total, k=N_GENE_CLUSTERS, n_pcs=N_PCS):
     n_t = int(dc.tp_off_host[t + 1] - dc.tp_off_host[t])
     mean, std = dc.lognorm_stats(genes, total, CLUSTER_TARGET, t=t)
     Z = dc.scale_write(genes, total, CLUSTER_TARGET, mean, std, clip=float(np.sqrt(n_t / 30.0)), t=t)   # [N_t, S]
-    M = Z.to(torch.float64).T                                                                               # genes x spots
-    M = M - M.mean(0, keepdim=True)                                                # PCA centres each variable (spot)
-    npc = min(n_pcs, genes.size, n_t)
-    if genes.size <= n_t:
-        w, V = torch.linalg.eigh(M @ M.T)                  # ascending eigenvalues; scores = V sqrt(w)
-        w, V = w.flip(0)[:npc], V.flip(1)[:, :npc]
-        pcs = V * w.clamp(min=0).sqrt()[None, :]
-    else:
-        w, U = torch.linalg.eigh(M.T @ M)                  # spot-side vectors; scores = M U
-        pcs = M @ U.flip(1)[:, :npc]
+    pcs = _pca_scores(Z.to(torch.float64).T, min(n_pcs, genes.size, n_t))                   # genes x spots -> genes x npc
     kk = min(k, genes.size)
     km = KMeansDevice(kk, random_state=1993, n_init=10).fit(pcs.contiguous())
     return np.asarray(km.labels_, dtype=np.int64)

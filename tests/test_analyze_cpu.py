@@ -161,7 +161,7 @@ def test_sweep_draws_are_those_of_the_single_fit():
         first, U = sweep_draws(n, k, 1993, 10)
         trials = 2 + int(np.log(k))
         seeds = np.random.RandomState(1993).randint(np.iinfo(np.int32).max, size=10)
-        for r, s in enumerate(seeds):          # KMeansDevice._init_centers' call order
+        for r, s in enumerate(seeds):          # the call order of tests/kmeans_ref.init_centers (sklearn's)
             g = np.random.RandomState(int(s))
             assert first[r] == int(g.choice(n))
             want = np.concatenate([g.uniform(size=trials) for _ in range(1, k)]) if k > 1 else np.zeros(0)
