@@ -312,7 +312,9 @@ int spadot_stamp(unsigned long long *buf, int slot, void *stream);
  * restarts whose done flag is set are left alone entirely (their centres are final; inertia[r] then still belongs to the
  * centres of the iteration that froze them -- measure the final one with a call that has skip_done = 0 and every done flag
  * set).  xoff, npts: int32 device arrays [sets]; rgroup, Kr: int32 device arrays [R]; tol: fp64 device array [sets].
- * K_max <= 32, D <= 32, (K_max + 256) * D <= 7936.  (KMeans of _train_utils.py:255-269 and _analyze_utils.py:42-105.) */
+ * K_max <= 32 and (K_max + 256) * D <= 7936 (K_max centres and 256 points in LDS), hence D <= 30; R <= 65535; anything else
+ * returns -22 and launches nothing.  An EMPTY cluster keeps its centre (sklearn relocates it).  (KMeans of
+ * _train_utils.py:255-269 and _analyze_utils.py:42-105.) */
 int spadot_lloyd_step(const double *X, double *C, const int *xoff, const int *npts, int n_max, int R, const int *rgroup,
                       const int *Kr, int K_max, int D, const double *tol, double *part, int *done, double *inertia, int skip_done,
                       void *stream);
@@ -325,7 +327,7 @@ int spadot_lloyd_step(const double *X, double *C, const int *xoff, const int *np
  * workgroup scan (bitwise reproducible), rounded in a different order from torch.cumsum: a candidate can differ from the torch
  * path's only when a draw lies within rounding distance of a boundary.  Outputs: idx [P, K_max] int32 row indices (-1 in
  * padding rows and for an invalid problem), centers [P, K_max, D] fp64 (zero padding).  closest: work space of P * n_max
- * doubles.  D <= 32, K_max <= 32. */
+ * doubles.  D <= 32, K_max <= 32 (two more dimensions than spadot_lloyd_step holds). */
 int spadot_kmeanspp_seed(const double *X, const int *xoff, const int *npts, int D, int P, const int *pset, const int *pK,
                          const int *pfirst, const int *puoff, const double *U, int K_max, int n_max, double *closest, int *idx,
                          double *centers, void *stream);

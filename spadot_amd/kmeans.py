@@ -12,9 +12,11 @@ the list, so a set fitted on its own and the same set fitted in a batch give the
 KMeansDevice(k).fit(X) (one set, one k), fit_many(Xs, k) (the per-epoch refit of every time point: the plan is cached and
 replayed as hipGraphs) and fit_sweep(Xs, ks) (the analyze stage's sweep over k: DESIGN 7b).
 
-Parity: sklearn's fit is third-party and not pinned bit for bit (its own chunked arithmetic decides ties and
-the exact iteration count); what IS exact is the assignment rule -- labels are produced by the
-spadot_kmeans_assign kernel (nearest centre, first minimum wins), the same rule sklearn's predict applies.
+Parity: sklearn's random draws are not reproduced (it draws the first centre with p=weights), so single restarts start
+elsewhere; everything AFTER the draws is pinned by tests/test_kmeans_kernels_gpu.py to a host reference and through it to
+sklearn.cluster.KMeans(init=<the seeded centres>, n_init=1): inertia, labels and iteration count, except where a cluster
+empties (it keeps its centre here, sklearn relocates it).  Labels are produced by the spadot_kmeans_assign kernel (nearest
+centre, first minimum wins), the same rule sklearn's predict applies.
 Selected by model_config['kmeans_backend']: 'device' (default) | 'sklearn' (the reference's host fit, the parity option).
 """
 import numpy as np
@@ -31,9 +33,10 @@ SEED_TORCH_MAX_PROBLEMS = 100
 
 
 def check_sweep_shape(d, k_max):
-    """ValueError unless the device K-means can fit k_max clusters in d dimensions (K <= 32, D <= 32, LDS budget)."""
-    if not 1 <= d <= 32:
-        raise ValueError(f"the device K-means supports data of 1 to 32 dimensions (got {d})")
+    """ValueError unless the device K-means can fit k_max clusters in d dimensions: K <= 32 and the Lloyd launch's LDS budget
+    (k_max + 256) * d <= 7936, which admits d <= 30 (the seeding kernel alone would take 32)."""
+    if not 1 <= d <= 30:
+        raise ValueError(f"the device K-means supports data of 1 to 30 dimensions (got {d})")
     if not 1 <= k_max <= 32:
         raise ValueError(f"the device K-means supports 1 to 32 clusters (got {k_max})")
     if (k_max + 256) * d > SWEEP_LDS_DOUBLES:
@@ -259,6 +262,8 @@ def _plan(Xs, ks, random_state, n_init, max_iter, tol, check_every, labels_for):
             if not 1 <= k <= ns[t]:
                 raise ValueError(f"k = {k} clusters on data set {t} of {ns[t]} points")
     pairs = [(t, k) for t, kt in enumerate(ks) for k in kt]
+    if not 1 <= len(pairs) * int(n_init) <= 65535:
+        raise ValueError(f"{len(pairs)} (data set, k) pairs x {n_init} restarts: one Lloyd launch holds 1 to 65535 restarts")
     want = set(pairs) if labels_for is True else set((int(t), int(k)) for t, k in (labels_for or ()))
     return _Plan(Xs[0].device, ns, d, ks, n_init, random_state, max_iter, tol, check_every, Xs[0].dtype, want)
 
