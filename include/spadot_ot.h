@@ -147,6 +147,18 @@ int spadot_ot_plan_host(spadot_ot_solver *s, double *plan_host);
  * one-hot(row labels)^T Q is the cluster transition table of the analyze stage (_analyze_utils.py:131-137). */
 int spadot_ot_plan_group_sums_dev(spadot_ot_solver *s, const int *col_labels_dev, int ngroups, double *Q_dev);
 
+/* The plan Pi = diag(a) K diag(b) / J of the last solve times a skinny dense matrix, without forming it:
+ *   transpose == 0 (pull back):     Q [I x nrhs] = Pi   P,  P is [J x nrhs]
+ *   transpose == 1 (push forward):  Q [J x nrhs] = Pi^T P,  P is [I x nrhs]
+ * P and Q are row-major fp64 device arrays without padding (they must not overlap), 1 <= nrhs <= 64; P may hold any finite
+ * values.  Both storages; products and sums in fp64.  Runs on the solver's stream and synchronises nothing.  No atomics: every
+ * output element is summed in an order that depends on the shape alone, so two calls give the same bits and a column's bits
+ * do not depend on the columns beside it.  The first call on a solver allocates one work space for the partial sums (at most
+ * about 64 * 8 B * (2 * max(I, J) + 2048 * 64), some 70 MB: it does not grow with I * J); later calls allocate nothing.
+ * Returns 0, -22 for a bad argument (null pointer, nrhs outside 1..64, transpose not 0 or 1: nothing is launched), -5 on a
+ * HIP failure. */
+int spadot_ot_plan_apply_dev(spadot_ot_solver *s, int transpose, const double *P_dev, int nrhs, double *Q_dev);
+
 /* Row sums of the plan (what compute_transport_map feeds back as growth, ot_solvers.py:117). */
 int spadot_ot_plan_rowsums_host(spadot_ot_solver *s, double *rowsums_host);
 

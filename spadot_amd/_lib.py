@@ -139,6 +139,8 @@ def ot_lib():
     lib.spadot_ot_plan_dev.restype = ci
     lib.spadot_ot_plan_group_sums_dev.argtypes = [vp, vp, ci, vp]
     lib.spadot_ot_plan_group_sums_dev.restype = ci
+    lib.spadot_ot_plan_apply_dev.argtypes = [vp, ci, vp, ci, vp]
+    lib.spadot_ot_plan_apply_dev.restype = ci
     lib.spadot_ot_plan_host.argtypes = [vp, vp]
     lib.spadot_ot_plan_host.restype = ci
     lib.spadot_ot_plan_rowsums_host.argtypes = [vp, vp]

@@ -3,7 +3,7 @@ point (a fixed k per time point, or the adaptive elbow rule over k = 4 .. 20), t
 consecutive time points and its domain transition tables, and the plots.
 
 Arguments (the reference's): data, output_dir (default: the data file's directory), prefix ('adaptive_' when n_clusters is
-None and the prefix is empty), n_clusters (one k per time point, or None); added: device ('cuda:0'), write_tmaps (False).
+None and the prefix is empty), n_clusters (one k per time point, or None); added: device ('cuda:0'), write_tmaps (False), lineage (False).
 
 Input: the latent.npz `train` always writes (X, rows, timepoint, spatial), latent.h5ad where `anndata` is importable, or an
 in-memory object with .X, .obs['timepoint'], .obsm['spatial'].  Time points are taken sorted; days are their positions.
@@ -14,6 +14,14 @@ Outputs in output_dir:
   {prefix}transition_table_{d}_{d+1}.csv/.npz  analyze_ot.write_transition_tables (also OT_g.txt, OT/tmap_*.npz on request);
                                                .h5ad with the reference's names where anndata is importable
   {prefix}{tp}_WSS_vs_Clusters.png, {prefix}{tp}_domains.png, {prefix}transition_dotplot_{d}_{d+1}.png   (with matplotlib)
+With lineage (spadot_amd.lineage: the plans of all pairs stay on the device and are chained, none is formed or solved twice):
+  {prefix}transition_table_{d}_{e}.csv/.npz    for every e > d + 1: the long-range table, in the layout of the consecutive ones
+                                               (.h5ad and transition_dotplot_{d}_{e}.png under the same conditions)
+  {prefix}trajectories.npz                     X [N, sum_t K_t] in input row order, rows, timepoint, names ('<tp>_<domain>' per
+                                               column: time points sorted, domains ascending): per domain, the distribution of
+                                               its ancestors / descendants over the spots of every time point
+  {prefix}fates.npz                            X [N, K_last], rows, timepoint, names: per spot, the share of its mass that ends in
+                                               each domain of the last time point (the last time point's rows: their own domain)
 
 The whole K-means work of the stage (17 k x 10 restarts per time point in adaptive mode) is ONE kmeans.fit_sweep call on the
 MI355X; the reference refits the chosen k with the same seed, which reproduces the sweep's own fit for that k, so the labels
@@ -81,6 +89,7 @@ def analyze(args):
     prefix, out = args.prefix, args.output_dir
     device = getattr(args, "device", None) or "cuda:0"
     write_tmaps = bool(getattr(args, "write_tmaps", False))
+    want_lineage = bool(getattr(args, "lineage", False))
 
     X = _dense(adata.X)
     tp_all = np.asarray(adata.obs["timepoint"])
@@ -121,10 +130,24 @@ def analyze(args):
 
     t0 = time.perf_counter()
     print("Optimal transport...")
-    tables = analyze_ot.write_transition_tables(out, latents, labels, tps, prefix=prefix, device=device,
-                                                write_tmaps=write_tmaps)
-    torch.cuda.synchronize(dev)
-    timings["ot"] = time.perf_counter() - t0
+    lin = None
+    if not want_lineage:
+        tables = analyze_ot.write_transition_tables(out, latents, labels, tps, prefix=prefix, device=device,
+                                                    write_tmaps=write_tmaps)
+        torch.cuda.synchronize(dev)
+        timings["ot"] = time.perf_counter() - t0
+    else:
+        from . import lineage
+        with lineage.TransportChain(latents, device=device) as chain:        # the same solves, kept
+            tables = analyze_ot.write_transition_tables(out, latents, labels, tps, prefix=prefix, device=device,
+                                                        write_tmaps=write_tmaps, chain=chain)
+            torch.cuda.synchronize(dev)
+            timings["ot"] = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            print("Lineages...")
+            lin = lineage.write_lineage(out, chain, labels, tps, masks, rows, tp_all, prefix=prefix)
+            torch.cuda.synchronize(dev)
+            timings["lineage"] = time.perf_counter() - t0
 
     t0 = time.perf_counter()
     import pandas as pd
@@ -135,13 +158,16 @@ def analyze(args):
                   "pixel_y": spatial[:, 1]}).to_csv(os.path.join(out, prefix + "domains.csv"), index=False)
     for tp, tab in zip(tps, wss_tables):
         tab.to_csv(os.path.join(out, prefix + str(tp) + "_WSS.csv"), index=False)
-    names = [([f"{tps[d]}_{c}" for c in range(tab.shape[0])], [f"{tps[d + 1]}_{c}" for c in range(tab.shape[1])])
-             for d, tab in enumerate(tables)]
+    pairs = [(d, d + 1, tab) for d, tab in enumerate(tables)]
+    if lin is not None:
+        pairs += [(d, e, tab) for (d, e), tab in sorted(lin["long_tables"].items())]
+    names = [([f"{tps[d]}_{c}" for c in range(tab.shape[0])], [f"{tps[e]}_{c}" for c in range(tab.shape[1])])
+             for d, e, tab in pairs]
     try:
         import anndata
-        for d, (tab, (obs, var)) in enumerate(zip(tables, names)):     # the reference's files (tools/npz_to_h5ad.py's mapping)
+        for (d, e, tab), (obs, var) in zip(pairs, names):              # the reference's files (tools/npz_to_h5ad.py's mapping)
             anndata.AnnData(np.asarray(tab), obs=pd.DataFrame(index=obs), var=pd.DataFrame(index=var)).write_h5ad(
-                os.path.join(out, f"{prefix}transition_table_{d}_{d + 1}.h5ad"))
+                os.path.join(out, f"{prefix}transition_table_{d}_{e}.h5ad"))
     except ImportError:
         pass
     if _analyze_utils.have_matplotlib():
@@ -151,11 +177,14 @@ def analyze(args):
                                         wss_tables[t]["wss"].tolist(), chosen[t])
             _analyze_utils.plot_domains(os.path.join(out, f"{prefix}{tp}_domains.png"), spatial[masks[t], 0],
                                         spatial[masks[t], 1], labels[t], tp)
-        for d, (tab, (obs, var)) in enumerate(zip(tables, names)):
-            _analyze_utils.plot_transition_dotplot(os.path.join(out, f"{prefix}transition_dotplot_{d}_{d + 1}.png"), tab, obs,
-                                                   var, d, d + 1)
+        for (d, e, tab), (obs, var) in zip(pairs, names):
+            _analyze_utils.plot_transition_dotplot(os.path.join(out, f"{prefix}transition_dotplot_{d}_{e}.png"), tab, obs,
+                                                   var, d, e)
     else:
         print("matplotlib not installed: no plots")
     timings["writing"] = time.perf_counter() - t0
     print("Results written to %s" % out)
-    return {"timepoints": tps, "labels": dict(zip(tps, labels)), "n_clusters": chosen, "tables": tables, "timings": timings}
+    res = {"timepoints": tps, "labels": dict(zip(tps, labels)), "n_clusters": chosen, "tables": tables, "timings": timings}
+    if lin is not None:
+        res["lineage"] = dict(lin, rows=rows, timepoint=tp_all)
+    return res

@@ -1053,6 +1053,114 @@ __global__ __launch_bounds__(256) void k_plan(const T *__restrict__ K, const dou
         out[(size_t)i * ldo + j] = (TO)((double)K[(size_t)i * ld + j] * a[i] * bj * scale);
 }
 
+// ------------------------------------------------------------------------------------------
+// The implicit plan times a skinny dense matrix: Q = Pi P (pull back) or Q = Pi^T P (push forward), Pi = diag(a) K diag(b)
+// * scale, P with NT = 1 .. 64 columns (nrhs rounded up to a power of two; the pad columns of Pp are 0).
+//
+// Both directions have one shape: a lane owns one OUTPUT row and keeps its NT sums in registers; the index that is
+// summed over is the same for the whole wave, so the row of P and the scaling that go with it arrive through uniform
+// loads and every product is one fp64 FMA with that operand.  The summed index is cut into bands (grid.y) so that about
+// two thousand waves are in flight; a band stores its NT partial sums per output row to ws[band][row][NT] and
+// k_apply_fin adds the bands in band order and applies the output-side scaling.  The band cut depends on the shape alone,
+// every sum has a fixed order, and there are no atomics: the same call gives the same bits, and a column's bits do not
+// depend on which other columns travel with it.  K is read once.
+//   push forward: lanes are columns j, K[i][j] is a coalesced row segment, the sum runs over the rows i of the band.
+//   pull back:    lanes are rows i; a 64 x TJ tile of K is loaded coalesced, turned through LDS (odd stride: no bank
+//                 conflicts) and read back one column per step, the sum runs over the columns j of the band.
+// ------------------------------------------------------------------------------------------
+constexpr int APPLY_WAVES = 2048;      // waves a launch aims at (8 per CU)
+
+template <typename T, int NT>
+__global__ __launch_bounds__(64) void k_apply_push(const T *__restrict__ K, const double *__restrict__ a,
+                                                   const double *__restrict__ Pp, double *__restrict__ ws, int I, int J,
+                                                   int ld, int rows_per_band) {
+    const int j = blockIdx.x * WAVE + threadIdx.x;          // < ld: the pad columns of K are addressable
+    const int band = blockIdx.y;
+    const int r0 = band * rows_per_band, r1 = min(I, r0 + rows_per_band);
+    double acc[NT];
+#pragma unroll
+    for (int r = 0; r < NT; r++) acc[r] = 0.0;
+    const T *col = K + j;
+#pragma unroll 4
+    for (int i = r0; i < r1; i++) {
+        const double ka = (double)col[(size_t)i * ld] * a[i];
+        const double *p = Pp + (size_t)i * NT;
+#pragma unroll
+        for (int r = 0; r < NT; r++) acc[r] = fma(ka, p[r], acc[r]);
+    }
+    if (j < J) {
+        double *o = ws + ((size_t)band * J + j) * NT;
+#pragma unroll
+        for (int r = 0; r < NT; r++) o[r] = acc[r];
+    }
+}
+
+template <typename T, int NT>
+__global__ __launch_bounds__(64) void k_apply_pull(const T *__restrict__ K, const double *__restrict__ b,
+                                                   const double *__restrict__ Pp, double *__restrict__ ws, int I, int J,
+                                                   int ld, int tiles_per_band) {
+    constexpr int TJ = 256 / (int)sizeof(T);                // columns per tile: one 256-byte row segment per load
+    constexpr int RPL = WAVE / TJ;                          // rows one wave-wide load covers
+    constexpr int LS = TJ + 1;                              // LDS row stride (odd)
+    __shared__ T tile[WAVE * LS];
+    const int lane = threadIdx.x;
+    const int i0 = blockIdx.x * WAVE, band = blockIdx.y;
+    const int lc = lane % TJ, lr = lane / TJ;
+    const int ntile = (J + TJ - 1) / TJ;
+    const int t0 = band * tiles_per_band, t1 = min(ntile, t0 + tiles_per_band);
+    double acc[NT];
+#pragma unroll
+    for (int r = 0; r < NT; r++) acc[r] = 0.0;
+    for (int t = t0; t < t1; t++) {
+        const int j0 = t * TJ;
+        const bool col_ok = j0 + lc < J;
+#pragma unroll 8
+        for (int rr = 0; rr < WAVE; rr += RPL) {
+            const int r = rr + lr, gi = i0 + r;
+            tile[r * LS + lc] = (col_ok && gi < I) ? K[(size_t)gi * ld + j0 + lc] : (T)0;
+        }
+        __syncthreads();
+        const int jn = min(TJ, J - j0);
+#pragma unroll(NT <= 8 ? 8 : NT <= 16 ? 4 : NT <= 32 ? 2 : 1)          // as many rows of P in flight as SGPRs hold
+        for (int jj = 0; jj < jn; jj++) {
+            const double kb = (double)tile[lane * LS + jj] * b[j0 + jj];
+            const double *p = Pp + (size_t)(j0 + jj) * NT;
+#pragma unroll
+            for (int r = 0; r < NT; r++) acc[r] = fma(kb, p[r], acc[r]);
+        }
+        __syncthreads();
+    }
+    const int row = i0 + lane;
+    if (row < I) {
+        double *o = ws + ((size_t)band * I + row) * NT;
+#pragma unroll
+        for (int r = 0; r < NT; r++) o[r] = acc[r];
+    }
+}
+
+// Pp [n x NT] <- P [n x nrhs], pad columns 0
+__global__ __launch_bounds__(256) void k_apply_pad(const double *__restrict__ P, int nrhs, int NT, size_t n,
+                                                   double *__restrict__ Pp) {
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n * NT) return;
+    const size_t row = t / NT;
+    const int r = (int)(t - row * NT);
+    Pp[t] = r < nrhs ? P[row * nrhs + r] : 0.0;
+}
+
+// Q[row][r] = (sum over bands, in band order, of ws[band][row][r]) * vec[row] * scale
+__global__ __launch_bounds__(256) void k_apply_fin(const double *__restrict__ ws, int nbands, size_t n, int NT, int nrhs,
+                                                   const double *__restrict__ vec, double scale, double *__restrict__ Q) {
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n * NT) return;
+    const size_t row = t / NT;
+    const int r = (int)(t - row * NT);
+    if (r >= nrhs) return;
+    double s = 0.0;
+    for (int k = 0; k < nbands; k++) s += ws[(size_t)k * n * NT + t];
+    Q[row * nrhs + r] = s * vec[row] * scale;
+}
+
 // dst (I x ldd, TD) <- src (I x lds, TS), columns < J; pad columns of dst <- 0
 template <typename TS, typename TD>
 __global__ __launch_bounds__(256) void k_convert(const TS *__restrict__ src, int lds,
@@ -1172,6 +1280,8 @@ struct spadot_ot_solver {
     long long cost_info[2] = {0, 0};   // last set_cost_from_latents: {path, candidates collected} (ot_cost.hip)
     void *cost_ws = nullptr;           // its scratch (sample, bracket candidates, sort space), kept between calls
     size_t cost_ws_bytes = 0;
+    double *apply_ws = nullptr;        // spadot_ot_plan_apply_dev: padded P and the band partials; taken at the first call, grows only
+    size_t apply_ws_count = 0;         // (doubles)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     size_t elt() const { return storage == SPADOT_F32 ? 4 : 8; }
 };
@@ -1750,7 +1860,7 @@ void spadot_ot_destroy(spadot_ot_solver *s) {
     SPADOT_ENTER
     if (!s) return;
     (void)hipStreamSynchronize(s->stream);
-    void *dev[] = {s->C, s->K, s->a, s->backup, s->red, s->part, s->rt, s->scal, s->flags, s->cost_ws, s->ctl};
+    void *dev[] = {s->C, s->K, s->a, s->backup, s->red, s->part, s->rt, s->scal, s->flags, s->cost_ws, s->ctl, s->apply_ws};
     for (void *p : dev) if (p) (void)hipFree(p);
     if (s->h_ctl) (void)hipHostFree(s->h_ctl);
     if (s->h_scal) (void)hipHostFree(s->h_scal);
@@ -1987,6 +2097,76 @@ int spadot_ot_plan_group_sums_dev(spadot_ot_solver *s, const int *col_labels_dev
         hipLaunchKernelGGL(k_plan_group_sums<float>, g, dim3(256), lds, s->stream, (const float *)s->K, s->a, s->b, col_labels_dev, ngroups, sc, Q_dev, s->I, s->J, s->ld);
     else
         hipLaunchKernelGGL(k_plan_group_sums<double>, g, dim3(256), lds, s->stream, (const double *)s->K, s->a, s->b, col_labels_dev, ngroups, sc, Q_dev, s->I, s->J, s->ld);
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+    SPADOT_LEAVE(SPADOT_EHIP)
+}
+
+// Q = Pi P (transpose == 0, P is J x nrhs, Q is I x nrhs) or Q = Pi^T P (transpose == 1, P is I x nrhs, Q is J x nrhs) for
+// the plan Pi = diag(a) K diag(b) / J of the last solve, which is never formed.  Three launches on the solver's stream
+// (pad P to NT columns when nrhs is no power of two, the band kernel, the band sum); nothing is synchronised.
+extern "C++" {
+namespace {
+// Bands of the summed index of spadot_ot_plan_apply_dev: rows of K pushing forward, 256-byte tiles of a row of K pulling
+// back.  A function of the shape and the storage alone (never of nrhs), so that a column's bits do not depend on its company.
+int apply_bands(const spadot_ot_solver *s, int transpose, int *per_band) {
+    const int units = transpose ? s->I : (int)(((size_t)s->J * s->elt() + 255) / 256);
+    const int groups = transpose ? s->ld / WAVE : (s->I + WAVE - 1) / WAVE;          // waves per band
+    const int min_units = transpose ? 16 : 1;                                        // at least 16 rows per band
+    const int want = std::max(1, std::min(APPLY_WAVES / groups, std::max(1, units / min_units)));
+    *per_band = (units + want - 1) / want;
+    return (units + *per_band - 1) / *per_band;
+}
+template <typename T, int NT>
+void launch_apply(spadot_ot_solver *s, int transpose, const double *Pp, double *part, int nbands, int per_band) {
+    if (transpose)
+        hipLaunchKernelGGL((k_apply_push<T, NT>), dim3(s->ld / WAVE, nbands), dim3(WAVE), 0, s->stream, (const T *)s->K, s->a, Pp,
+                           part, s->I, s->J, s->ld, per_band);
+    else
+        hipLaunchKernelGGL((k_apply_pull<T, NT>), dim3((s->I + WAVE - 1) / WAVE, nbands), dim3(WAVE), 0, s->stream,
+                           (const T *)s->K, s->b, Pp, part, s->I, s->J, s->ld, per_band);
+}
+template <typename T>
+void launch_apply_T(spadot_ot_solver *s, int transpose, int NT, const double *Pp, double *part, int nbands, int per_band) {
+    switch (NT) {
+    case 1: launch_apply<T, 1>(s, transpose, Pp, part, nbands, per_band); break;
+    case 2: launch_apply<T, 2>(s, transpose, Pp, part, nbands, per_band); break;
+    case 4: launch_apply<T, 4>(s, transpose, Pp, part, nbands, per_band); break;
+    case 8: launch_apply<T, 8>(s, transpose, Pp, part, nbands, per_band); break;
+    case 16: launch_apply<T, 16>(s, transpose, Pp, part, nbands, per_band); break;
+    case 32: launch_apply<T, 32>(s, transpose, Pp, part, nbands, per_band); break;
+    default: launch_apply<T, 64>(s, transpose, Pp, part, nbands, per_band); break;
+    }
+}
+}  // namespace
+}  // extern "C++"
+
+int spadot_ot_plan_apply_dev(spadot_ot_solver *s, int transpose, const double *P_dev, int nrhs, double *Q_dev) {
+    SPADOT_ENTER
+    if (!s || !P_dev || !Q_dev || nrhs < 1 || nrhs > 64 || (transpose != 0 && transpose != 1)) return -22;
+    int NT = 1;
+    while (NT < nrhs) NT *= 2;
+    const size_t n_in = transpose ? s->I : s->J, n_out = transpose ? s->J : s->I;
+    int per_band = 0;
+    const int nbands = apply_bands(s, transpose, &per_band);
+    const size_t pad_count = NT != nrhs ? n_in * NT : 0;
+    if (!s->apply_ws) {        // first call: the one allocation of this entry, sized for 64 columns in either direction
+        int dummy = 0;
+        const size_t parts = std::max((size_t)apply_bands(s, 0, &dummy) * s->I, (size_t)apply_bands(s, 1, &dummy) * s->J);
+        s->apply_ws_count = 64 * ((size_t)std::max(s->I, s->J) + parts);
+        s->apply_ws = (double *)dmalloc(sizeof(double) * s->apply_ws_count);
+    }
+    if (pad_count + (size_t)nbands * n_out * NT > s->apply_ws_count) return -22;      // (cannot happen: see the sizing above)
+    const double *Pp = P_dev;
+    if (pad_count) {
+        hipLaunchKernelGGL(k_apply_pad, dim3((unsigned)((pad_count + 255) / 256)), dim3(256), 0, s->stream, P_dev, nrhs, NT, n_in,
+                           s->apply_ws);
+        Pp = s->apply_ws;
+    }
+    double *part = s->apply_ws + pad_count;
+    if (s->storage == SPADOT_F32) launch_apply_T<float>(s, transpose, NT, Pp, part, nbands, per_band);
+    else launch_apply_T<double>(s, transpose, NT, Pp, part, nbands, per_band);
+    hipLaunchKernelGGL(k_apply_fin, dim3((unsigned)((n_out * NT + 255) / 256)), dim3(256), 0, s->stream, part, nbands, n_out, NT,
+                       nrhs, transpose ? s->b : s->a, 1.0 / s->J, Q_dev);
     return hipGetLastError() == hipSuccess ? 0 : -5;
     SPADOT_LEAVE(SPADOT_EHIP)
 }

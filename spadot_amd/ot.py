@@ -147,6 +147,34 @@ class OTSolver:
         onehot[rl, torch.arange(self.I, device=self.device)] = 1.0
         return onehot @ Q
 
+    def apply(self, P, transpose=False):
+        """The plan of the last solve times a skinny dense matrix, on the device and without forming the plan
+        (spadot_ot_plan_apply_dev).  transpose=False pulls back: plan @ P for P [J, nrhs]; transpose=True pushes forward:
+        plan.T @ P for P [I, nrhs].  P: array or tensor on any device, cast to contiguous fp64; more than 64 columns go in
+        chunks of 64.  Returns a torch fp64 device tensor [I or J, nrhs]; a 1-D P is one column and returns 1-D."""
+        P = torch.as_tensor(P).to(self.device, torch.float64)
+        one_d = P.dim() == 1
+        if one_d:
+            P = P[:, None]
+        n_in, n_out = (self.I, self.J) if transpose else (self.J, self.I)
+        if P.dim() != 2 or P.shape[0] != n_in or P.shape[1] < 1:
+            raise ValueError(f"apply(transpose={bool(transpose)}) needs P of shape [{n_in}, nrhs >= 1], got {tuple(P.shape)}")
+        nrhs = int(P.shape[1])
+        chunks = [P[:, c0:c0 + 64].contiguous() for c0 in range(0, nrhs, 64)]
+        outs = []
+        self._stream.wait_stream(torch.cuda.current_stream(self.device))
+        for Pc in chunks:
+            Q = torch.empty((n_out, Pc.shape[1]), dtype=torch.float64, device=self.device)
+            rc = self.lib.spadot_ot_plan_apply_dev(self.h, 1 if transpose else 0, ctypes.c_void_p(Pc.data_ptr()),
+                                                   int(Pc.shape[1]), ctypes.c_void_p(Q.data_ptr()))
+            if rc != 0:
+                raise RuntimeError(f"plan_apply failed with {rc}")
+            Pc.record_stream(self._stream); Q.record_stream(self._stream)
+            outs.append(Q)
+        torch.cuda.current_stream(self.device).wait_stream(self._stream)
+        Q = outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
+        return Q[:, 0] if one_d else Q
+
     def plan_rowsums(self):
         r = np.empty(self.I, dtype=np.float64)
         rc = self.lib.spadot_ot_plan_rowsums_host(self.h, r.ctypes.data_as(ctypes.c_void_p))
