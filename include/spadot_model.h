@@ -16,6 +16,7 @@
  *   spadot_kmeans_*    utils/_train_utils.py:240-253 (loss) and sklearn KMeans.predict (labels, :266-269)
  *   spadot_adamw_*     utils/_train_utils.py:214-217 (clip_grad_norm_(0.3) + AdamW.step)
  *   spadot_pre_*, spadot_sparkx_*  utils/_utils.py:121-414 (SPARK-X) and utils/_preprocess_utils.py:11-49 (the preprocess stage)
+ *   spadot_mk_*        no counterpart in the reference: scipy.stats.mannwhitneyu per (time point, gene, domain)
  */
 #ifndef SPADOT_MODEL_H
 #define SPADOT_MODEL_H
@@ -639,6 +640,28 @@ int spadot_sct_resid_write(const long long *colptr, const int *ridx, const float
                            const int *genes, const double *lur, const double *lu, const int *krow, const int *rowmap, int N,
                            const double *pars, const double *center, double clip_lo, double *out, void *stream);
 int spadot_sct_polygamma(const double *x, int n, double *psi, double *psi1, void *stream);
+
+/* ---------------------------------------------------------------- markers stage (csrc/markers.hip)
+ * Per (time point, gene, domain) Wilcoxon rank-sum tests of v = float(log1p(x * target / total[r])), all spots of the time point
+ * ranked together with average ranks, fp32 bit patterns defining ties: scipy.stats.mannwhitneyu(in, out, 'two-sided',
+ * method='asymptotic', use_continuity=True).  Same CSC layout as the preprocess stage; labels[r] in 0 .. K-1 is the domain of
+ * row r inside its time point, nk[t, k] the size of domain k.  Limits (return -7): K <= 32, nmax <= 2097151.
+ *
+ * mk_lognorm:  v[p] per stored entry p of the CSC arrays
+ * mk_ranksum:  per (t, g): r2[t, g, K] int64 TWICE the rank sum of each domain, ties[t, g] int64 sum of t^3 - t over the tie
+ *              runs (the zeros included), nnz_k[t, g, K] int32 entries with v > 0, vsum[t, g, K] fp64 sum of v (fixed order).
+ *              Segments of up to spadot_mk_lds_capacity() entries are sorted in LDS, longer ones through `scratch`
+ *              (spadot_mk_ranksum_scratch_bytes(T, G, nmax) bytes, nmax >= the spots of every time point)
+ * mk_finish:   u1, score, pval [t, g, K] fp64; score 0 and p 1 where the variance is 0, a side is empty or U1 = n1 n2 / 2 */
+int spadot_mk_lds_capacity(void);
+long long spadot_mk_ranksum_scratch_bytes(int T, int G, int nmax);
+int spadot_mk_lognorm(const int *ridx, const float *val, const double *total, long long nnz, double target, float *v,
+                      void *stream);
+int spadot_mk_ranksum(const long long *colptr, const int *ridx, const float *v, const int *tp_off, const int *labels,
+                      const int *nk, int T, int G, int K, int nmax, void *scratch, long long scratch_bytes, long long *r2,
+                      long long *ties, int *nnz_k, double *vsum, void *stream);
+int spadot_mk_finish(const long long *r2, const long long *ties, const int *tp_off, const int *nk, int T, int G, int K,
+                     double *u1, double *score, double *pval, void *stream);
 
 #ifdef __cplusplus
 }

@@ -270,6 +270,9 @@ def model_lib():
         "spadot_sct_resid_stats": [vp, vp, vp, vp, ci, ci, vp, vp, vp, ci, vp, cd, cd, vp, vp],
         "spadot_sct_resid_write": [vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, cd, vp, vp],
         "spadot_sct_polygamma": [vp, ci, vp, vp, vp],
+        "spadot_mk_lognorm": [vp, vp, vp, ll, cd, vp, vp],
+        "spadot_mk_ranksum": [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, ll, vp, vp, vp, vp, vp],
+        "spadot_mk_finish": [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -285,6 +288,10 @@ def model_lib():
     lib.spadot_gemm_wgrad_bf16_workspace.restype = ll
     lib.spadot_gemm_wgrad_bf16_workspace_tiled.argtypes = [ci, ci, ci, ci, ci]
     lib.spadot_gemm_wgrad_bf16_workspace_tiled.restype = ll
+    lib.spadot_mk_lds_capacity.argtypes = []
+    lib.spadot_mk_lds_capacity.restype = ci
+    lib.spadot_mk_ranksum_scratch_bytes.argtypes = [ci, ci, ci]
+    lib.spadot_mk_ranksum_scratch_bytes.restype = ll
     _seal(lib)
     lib._spadot_ready = True
     return lib
