@@ -17,6 +17,7 @@
  *   spadot_adamw_*     utils/_train_utils.py:214-217 (clip_grad_norm_(0.3) + AdamW.step)
  *   spadot_pre_*, spadot_sparkx_*  utils/_utils.py:121-414 (SPARK-X) and utils/_preprocess_utils.py:11-49 (the preprocess stage)
  *   spadot_mk_*        no counterpart in the reference: scipy.stats.mannwhitneyu per (time point, gene, domain)
+ *   spadot_silhouette  no counterpart in the reference: sklearn.metrics.silhouette_samples per (data set, labeling)
  */
 #ifndef SPADOT_MODEL_H
 #define SPADOT_MODEL_H
@@ -662,6 +663,21 @@ int spadot_mk_ranksum(const long long *colptr, const int *ridx, const float *v, 
                       long long *ties, int *nnz_k, double *vsum, void *stream);
 int spadot_mk_finish(const long long *r2, const long long *ties, const int *tp_off, const int *nk, int T, int G, int K,
                      double *u1, double *score, double *pval, void *stream);
+
+/* ---------------------------------------------------------------- silhouette coefficients (csrc/silhouette.hip)
+ * sklearn.metrics.silhouette_samples of P (data set, labeling) problems in one launch, fp64, no n x n matrix, no atomics (two
+ * runs, and a problem alone or in a batch, give the same bits).  x: [rows, d] fp64, the data sets one after the other.
+ * prob[p, 4] int64: first row of the problem's set in x, offset of the problem in order / the outputs, n (points), K (label
+ * values).  order[offset + j]: the set's row at position j of the problem's points sorted by (label, row); coff[p, 33] int32:
+ * cluster k holds the sorted positions coff[p, k] .. coff[p, k + 1] (coff[p, K] = n; an empty cluster is skipped).
+ * With dist(i, j) = sqrt(sum_c (x_ic - x_jc)^2) and S_i(k) the sum of dist(i, j) over cluster k, per row i of cluster c:
+ *   a = S_i(c) / (n_c - 1) (0 if n_c = 1),  b = min over non-empty k != c of S_i(k) / n_k,  nearest = that k (first minimum),
+ *   s = (b - a) / max(a, b), 0 if n_c = 1 or max(a, b) = 0;  a single non-empty cluster leaves b = inf, nearest = -1, s = NaN.
+ * Outputs a, b, s fp64 and nearest int32 at [offset + row], the caller's row order.
+ * Limits (return -7, nothing launched): 1 <= d <= 32, 2 <= k_min <= k_max <= 32 (the range of the K column), P <= 65535
+ * (gridDim.y), n_max <= 2147483391 (int32 positions; n_max >= the n of every problem sizes gridDim.x). */
+int spadot_silhouette(const double *x, int d, int P, const long long *prob, const int *order, const int *coff, int n_max,
+                      int k_min, int k_max, double *a, double *b, int *nearest, double *s, void *stream);
 
 #ifdef __cplusplus
 }

@@ -273,6 +273,7 @@ def model_lib():
         "spadot_mk_lognorm": [vp, vp, vp, ll, cd, vp, vp],
         "spadot_mk_ranksum": [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, ll, vp, vp, vp, vp, vp],
         "spadot_mk_finish": [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp],
+        "spadot_silhouette": [vp, ci, ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)

@@ -3,7 +3,9 @@ point (a fixed k per time point, or the adaptive elbow rule over k = 4 .. 20), t
 consecutive time points and its domain transition tables, and the plots.
 
 Arguments (the reference's): data, output_dir (default: the data file's directory), prefix ('adaptive_' when n_clusters is
-None and the prefix is empty), n_clusters (one k per time point, or None); added: device ('cuda:0'), write_tmaps (False), lineage (False).
+None and the prefix is empty), n_clusters (one k per time point, or None); added: device ('cuda:0'), write_tmaps (False),
+lineage (False), criterion ('elbow' | 'silhouette': how the adaptive mode picks k; 'silhouette' scores all 17 fits of every
+time point in one spadot_amd.silhouette.silhouette_many call and takes the k with the largest score).
 
 Input: the latent.npz `train` always writes (X, rows, timepoint, spatial), latent.h5ad where `anndata` is importable, or an
 in-memory object with .X, .obs['timepoint'], .obsm['spatial'].  Time points are taken sorted; days are their positions.
@@ -11,9 +13,12 @@ in-memory object with .X, .obs['timepoint'], .obsm['spatial'].  Time points are 
 Outputs in output_dir:
   {prefix}domains.csv                          one row per input spot, in input order: row, timepoint, kmeans, pixel_x, pixel_y
   {prefix}{tp}_WSS.csv                         (adaptive) clusters, wss, wss_diff, wss_diff_ratio, selected
+  {prefix}{tp}_silhouette.csv                  (adaptive, criterion silhouette) clusters, silhouette, selected; the WSS table's
+                                               `selected` then marks the k the silhouette rule chose
   {prefix}transition_table_{d}_{d+1}.csv/.npz  analyze_ot.write_transition_tables (also OT_g.txt, OT/tmap_*.npz on request);
                                                .h5ad with the reference's names where anndata is importable
   {prefix}{tp}_WSS_vs_Clusters.png, {prefix}{tp}_domains.png, {prefix}transition_dotplot_{d}_{d+1}.png   (with matplotlib)
+  {prefix}{tp}_silhouette_vs_Clusters.png      (criterion silhouette, with matplotlib)
 With lineage (spadot_amd.lineage: the plans of all pairs stay on the device and are chained, none is formed or solved twice):
   {prefix}transition_table_{d}_{e}.csv/.npz    for every e > d + 1: the long-range table, in the layout of the consecutive ones
                                                (.h5ad and transition_dotplot_{d}_{e}.png under the same conditions)
@@ -76,6 +81,11 @@ def validate(n_clusters, counts, d):
 
 
 def analyze(args):
+    criterion = getattr(args, "criterion", "elbow") or "elbow"
+    if criterion not in ("elbow", "silhouette"):
+        raise ValueError(f"criterion must be 'elbow' or 'silhouette', not {criterion!r}")
+    if criterion == "silhouette" and getattr(args, "n_clusters", None) is not None:
+        raise ValueError("--criterion silhouette chooses the number of clusters: it cannot be combined with --n_clusters")
     print("Loading latent representations...")
     adata, path = _utils.load_data(args.data)
     if not getattr(args, "output_dir", None):
@@ -111,10 +121,25 @@ def analyze(args):
     latents = [np.ascontiguousarray(X[m]) for m in masks]
     Xs = [torch.as_tensor(x, device=dev) for x in latents]
     adaptive = n_clusters is None
-    res = kmeans.fit_sweep(Xs, ks, random_state=1993, n_init=10, labels_for=None if adaptive else True)
-    chosen, labels, wss_tables = [], [], []
+    by_silhouette = adaptive and criterion == "silhouette"
+    res = kmeans.fit_sweep(Xs, ks, random_state=1993, n_init=10, labels_for=None if adaptive and not by_silhouette else True)
+    sil_scores = None
+    if by_silhouette:                                     # all T x 17 labelings of the sweep: one launch
+        from .silhouette import silhouette_many
+        t1 = time.perf_counter()
+        sil = silhouette_many(Xs, [[res[t][k].labels_ for k in ADAPTIVE_KS] for t in range(len(tps))],
+                              n_clusters=[list(ADAPTIVE_KS) for _ in tps])
+        sil_scores = [[r.score for r in st] for st in sil]
+        timings["silhouette"] = time.perf_counter() - t1      # the results are on the host: the launch has finished
+    chosen, labels, wss_tables, sil_tables = [], [], [], []
     for t, tp in enumerate(tps):
-        if adaptive:
+        if by_silhouette:
+            wss = [res[t][k].inertia_ for k in ADAPTIVE_KS]
+            k = _analyze_utils.select_k_silhouette(sil_scores[t], timepoint=tp)
+            wss_tables.append(_analyze_utils.wss_table(wss, k))
+            sil_tables.append(_analyze_utils.silhouette_table(sil_scores[t], k))
+            lab = res[t][k].labels_
+        elif adaptive:
             wss = [res[t][k].inertia_ for k in ADAPTIVE_KS]
             k = _analyze_utils.select_k(wss, timepoint=tp)
             wss_tables.append(_analyze_utils.wss_table(wss, k))
@@ -158,6 +183,8 @@ def analyze(args):
                   "pixel_y": spatial[:, 1]}).to_csv(os.path.join(out, prefix + "domains.csv"), index=False)
     for tp, tab in zip(tps, wss_tables):
         tab.to_csv(os.path.join(out, prefix + str(tp) + "_WSS.csv"), index=False)
+    for tp, tab in zip(tps, sil_tables):
+        tab.to_csv(os.path.join(out, prefix + str(tp) + "_silhouette.csv"), index=False)
     pairs = [(d, d + 1, tab) for d, tab in enumerate(tables)]
     if lin is not None:
         pairs += [(d, e, tab) for (d, e), tab in sorted(lin["long_tables"].items())]
@@ -175,6 +202,9 @@ def analyze(args):
             if adaptive:
                 _analyze_utils.plot_wss(os.path.join(out, f"{prefix}{tp}_WSS_vs_Clusters.png"), ADAPTIVE_KS,
                                         wss_tables[t]["wss"].tolist(), chosen[t])
+            if by_silhouette:
+                _analyze_utils.plot_silhouette(os.path.join(out, f"{prefix}{tp}_silhouette_vs_Clusters.png"), ADAPTIVE_KS,
+                                               sil_scores[t], chosen[t])
             _analyze_utils.plot_domains(os.path.join(out, f"{prefix}{tp}_domains.png"), spatial[masks[t], 0],
                                         spatial[masks[t], 1], labels[t], tp)
         for (d, e, tab), (obs, var) in zip(pairs, names):
@@ -185,6 +215,9 @@ def analyze(args):
     timings["writing"] = time.perf_counter() - t0
     print("Results written to %s" % out)
     res = {"timepoints": tps, "labels": dict(zip(tps, labels)), "n_clusters": chosen, "tables": tables, "timings": timings}
+    if by_silhouette:
+        res["silhouette"] = dict(zip(tps, sil_scores))
+        res["criterion"] = criterion
     if lin is not None:
         res["lineage"] = dict(lin, rows=rows, timepoint=tp_all)
     return res

@@ -1835,6 +1835,29 @@ def kmeans_assign(x, centers):
     return labels
 
 
+def silhouette_launch(X, prob, order, coff, n_max, k_min, k_max, out=None):
+    """Silhouette coefficients of P (data set, labeling) problems in ONE launch (include/spadot_model.h: spadot_silhouette).
+    X [rows, d] fp64, the sets one after the other; prob [P, 4] int64 (first row of the set, offset of the problem, n, K);
+    order int32 [sum n]: per problem its rows sorted by (label, row); coff int32 [P, 33] cluster offsets.  Returns (a, b,
+    nearest, s) of length sum n in the caller's row order (out: tensors to write into).  ValueError outside 1 <= d <= 32,
+    2 <= K <= 32, P <= 65535, n <= 2147483391, before any launch."""
+    _need_cuda(X, prob, order, coff)
+    if X.dtype != torch.float64 or not X.is_contiguous():
+        raise RuntimeError("silhouette_launch takes a contiguous fp64 matrix")
+    total, P = int(order.shape[0]), int(prob.shape[0])
+    a, b, nearest, s = out if out is not None else (
+        torch.empty(total, dtype=torch.float64, device=X.device), torch.empty(total, dtype=torch.float64, device=X.device),
+        torch.empty(total, dtype=torch.int32, device=X.device), torch.empty(total, dtype=torch.float64, device=X.device))
+    rc = model_lib().spadot_silhouette(_p(X), int(X.shape[1]), P, _p(prob), _p(order), _p(coff), int(n_max), int(k_min),
+                                       int(k_max), _p(a), _p(b), _p(nearest), _p(s), _stream())
+    if rc == -7:
+        raise ValueError(f"spadot_silhouette: outside its limits (1 <= d <= 32, 2 <= K <= 32, at most 65535 problems of at "
+                         f"most 2147483391 points): d = {int(X.shape[1])}, K = {int(k_min)} .. {int(k_max)}, {P} problems, "
+                         f"n <= {int(n_max)}")
+    _check(rc, "spadot_silhouette")
+    return a, b, nearest, s
+
+
 # ----------------------------------------------------------------------------- optimiser
 
 def lloyd_steps(X, C, xoff, npts, n_max, rgroup, Kr, tol, done, inertia, part, steps, skip_done=False):

@@ -1,6 +1,6 @@
 """Host-side parts of the analyze stage: mirror of the reference's SpaDOT/utils/_analyze_utils.py.  The clustering itself
 runs on the device (spadot_amd.kmeans.fit_sweep); here are the elbow rule of Adaptive_clustering (:73-88) as a pure
-function, the WSS table, and the three plots (WSS curve :89-99, domains :140-164, transition dotplot :166-209), drawn with
+function, the silhouette rule of `--criterion silhouette` (no counterpart in the reference), the WSS table, and the plots (WSS curve :89-99, domains :140-164, transition dotplot :166-209), drawn with
 matplotlib's object API on an Agg canvas (no pyplot: global plotting state is left alone; seaborn is not needed)."""
 import numpy as np
 
@@ -54,6 +54,30 @@ def wss_table(wss, selected, min_clusters=MIN_CLUSTERS):
     return pd.DataFrame({"clusters": ks, "wss": w, "wss_diff": d, "wss_diff_ratio": ratio, "selected": ks == int(selected)})
 
 
+def select_k_silhouette(scores, min_clusters=MIN_CLUSTERS, max_clusters=MAX_CLUSTERS, timepoint=None):
+    """The silhouette rule of `analyze --criterion silhouette`: scores[i] is the silhouette score of the fit with
+    k = min_clusters + i; the k with the largest score wins, on ties the first, NaN (an undefined labeling) is skipped.
+    ValueError naming the time point when no score is defined."""
+    s = np.asarray(scores, dtype=np.float64).ravel()
+    if s.size != max_clusters - min_clusters + 1:
+        raise ValueError(f"select_k_silhouette needs one score per k = {min_clusters} .. {max_clusters} (got {s.size})")
+    ok = ~np.isnan(s)
+    if not ok.any():
+        where = f" at time point {timepoint}" if timepoint is not None else ""
+        raise ValueError(f"no fit{where} has a defined silhouette score (k = {min_clusters} .. {max_clusters}); give the "
+                         f"number of clusters per time point with --n_clusters")
+    idx = np.flatnonzero(ok)
+    return int(min_clusters + idx[int(np.argmax(s[idx]))])            # first maximum
+
+
+def silhouette_table(scores, selected, min_clusters=MIN_CLUSTERS):
+    """The silhouette table of one time point: columns clusters, silhouette, selected (a pandas DataFrame)."""
+    import pandas as pd
+    s = np.asarray(scores, dtype=np.float64).ravel()
+    ks = np.arange(min_clusters, min_clusters + s.size)
+    return pd.DataFrame({"clusters": ks, "silhouette": s, "selected": ks == int(selected)})
+
+
 def have_matplotlib():
     try:
         import matplotlib  # noqa: F401
@@ -80,6 +104,21 @@ def plot_wss(path, clusters, wss, k_selected):
     ax.set_title("WSS vs Number of Clusters")
     ax.set_xlabel("Number of Clusters")
     ax.set_ylabel("WSS")
+    ax.set_xticks(clusters)
+    ax.grid()
+    fig.savefig(path)
+
+
+def plot_silhouette(path, clusters, scores, k_selected):
+    """{prefix}{tp}_silhouette_vs_Clusters.png: the silhouette score of every k, the chosen one marked (as plot_wss)."""
+    clusters, scores = list(clusters), list(scores)
+    fig = _figure((10, 6))
+    ax = fig.add_subplot(1, 1, 1)
+    ax.plot(clusters, scores, marker="o")
+    ax.scatter(k_selected, scores[clusters.index(k_selected)], color="red", s=100, label="Selected Cluster")
+    ax.set_title("Silhouette score vs Number of Clusters")
+    ax.set_xlabel("Number of Clusters")
+    ax.set_ylabel("Silhouette score")
     ax.set_xticks(clusters)
     ax.grid()
     fig.savefig(path)
