@@ -18,6 +18,7 @@
  *   spadot_pre_*, spadot_sparkx_*  utils/_utils.py:121-414 (SPARK-X) and utils/_preprocess_utils.py:11-49 (the preprocess stage)
  *   spadot_mk_*        no counterpart in the reference: scipy.stats.mannwhitneyu per (time point, gene, domain)
  *   spadot_silhouette  no counterpart in the reference: sklearn.metrics.silhouette_samples per (data set, labeling)
+ *   spadot_weighted_moments  no counterpart in the reference: X_csc.T @ W of the log-normalised counts, three moments
  */
 #ifndef SPADOT_MODEL_H
 #define SPADOT_MODEL_H
@@ -678,6 +679,22 @@ int spadot_mk_finish(const long long *r2, const long long *ties, const int *tp_o
  * (gridDim.y), n_max <= 2147483391 (int32 positions; n_max >= the n of every problem sizes gridDim.x). */
 int spadot_silhouette(const double *x, int d, int P, const long long *prob, const int *order, const int *coff, int n_max,
                       int k_min, int k_max, double *a, double *b, int *nearest, double *s, void *stream);
+
+/* ---------------------------------------------------------------- trends stage (csrc/trends.hip)
+ * The log-normalised counts of every time point, transposed, times a dense row-major fp64 W[n, C] (rows in the permuted order of
+ * the CSC arrays), as three weighted moments in one pass over the stored entries.  Same CSC layout as the preprocess and markers
+ * stages; v: the fp32 values of spadot_mk_lognorm in CSC order.  With vd = (double)v and vv = vd * vd, over the stored entries
+ * (i, g) whose row i lies in time point t:
+ *   S0[t, g, c] = sum W[i, c],   S1[t, g, c] = sum vd W[i, c],   S2[t, g, c] = sum vv W[i, c]      (fp64 [T, G, C])
+ * A stored entry with v = 0 adds W to S0 and nothing to S1, S2; W may be negative.  One workgroup per (t, g); wavefront w of its
+ * four adds the segment's entries w, w + 4, ... in that order and the four partial sums are added as ((p0 + p1) + p2) + p3: no
+ * atomics, and the bits of an output element depend only on its segment and its column of W, not on C, T, G or the other
+ * columns (two runs, a column alone, a problem in another batch: the same bits).  No temporaries in global memory.
+ * spadot_weighted_moments_chunk(): the stored entries staged in LDS at a time (segments of any length are taken).
+ * Limits (return -7, nothing launched): 1 <= C <= 1024, n <= 2147483647, T * G <= 2147483647 (gridDim.x). */
+int spadot_weighted_moments_chunk(void);
+int spadot_weighted_moments(const long long *colptr, const int *ridx, const float *v, const int *tp_off, int T, int G,
+                            const double *W, long long n, int C, double *S0, double *S1, double *S2, void *stream);
 
 #ifdef __cplusplus
 }

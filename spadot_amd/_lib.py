@@ -274,6 +274,7 @@ def model_lib():
         "spadot_mk_ranksum": [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, ll, vp, vp, vp, vp, vp],
         "spadot_mk_finish": [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp],
         "spadot_silhouette": [vp, ci, ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp],
+        "spadot_weighted_moments": [vp, vp, vp, vp, ci, ci, vp, ll, ci, vp, vp, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -293,6 +294,8 @@ def model_lib():
     lib.spadot_mk_lds_capacity.restype = ci
     lib.spadot_mk_ranksum_scratch_bytes.argtypes = [ci, ci, ci]
     lib.spadot_mk_ranksum_scratch_bytes.restype = ll
+    lib.spadot_weighted_moments_chunk.argtypes = []
+    lib.spadot_weighted_moments_chunk.restype = ci
     _seal(lib)
     lib._spadot_ready = True
     return lib

@@ -7,6 +7,7 @@
                                  [--lineage] [--criterion elbow|silhouette]
     python -m spadot_amd markers -i COUNTS --domains CSV [-o DIR] [--prefix P] [--top 100] [--device cuda:0]
     python -m spadot_amd score   -i LATENT --domains CSV [-o DIR] [--prefix P] [--device cuda:0]
+    python -m spadot_amd trends  -i COUNTS [--trajectories NPZ] [--fates NPZ] [-o DIR] [--prefix P] [--top 100] [--device cuda:0]
 
 `preprocess` runs SPARK-X feature selection and the scaling on the device (spadot_amd.preprocess).  The balancing rule's gene
 clusters come from K-means by default; `--gene_clusters louvain` clusters SCTransform Pearson residuals with Louvain as the
@@ -15,7 +16,9 @@ device and chains them: long-range transition tables, the trajectories of every 
 (spadot_amd.lineage).  `markers` tests every gene against every domain of `analyze`'s domains.csv with a Wilcoxon
 rank-sum test on the device (spadot_amd.markers).  `score` gives every spot of `analyze`'s domains.csv its silhouette
 coefficient in the latent space and every domain and time point the mean; `analyze --criterion silhouette` picks the adaptive
-mode's k by the largest silhouette score instead of the elbow rule (spadot_amd.silhouette)."""
+mode's k by the largest silhouette score instead of the elbow rule (spadot_amd.silhouette).  `trends` reads the
+trajectories.npz and / or fates.npz of `analyze --lineage` against the counts: the weighted mean expression of every gene along
+every domain's trajectory, and the correlation of every gene with every fate (spadot_amd.trends)."""
 import argparse
 import os
 import sys
@@ -102,6 +105,22 @@ def build_parser():
                     help="Output directory. Default: the same as where the data locates.")
     sc.add_argument("--prefix", dest="prefix", type=str, default="", help="Prefix for the silhouette tables. Default: ''")
     sc.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
+
+    tn = sub.add_parser("trends", help="Gene trends along the trajectories of the domains and the genes that go with each fate.")
+    tn.add_argument("-i", "--data", dest="data", type=str, required=True,
+                    help="The counts: the .npz written by preprocess (its raw counts of the selected genes), or raw counts as "
+                         "preprocess reads them (.npz or .h5ad).")
+    tn.add_argument("--trajectories", dest="trajectories", type=str,
+                    help="The trajectories.npz written by analyze --lineage: weighted mean expression of every gene along every "
+                         "trajectory.")
+    tn.add_argument("--fates", dest="fates", type=str,
+                    help="The fates.npz written by analyze --lineage: correlation of every gene with every fate.")
+    tn.add_argument("-o", "--output_dir", dest="output_dir", type=str,
+                    help="Output directory. Default: the same as where the data locates.")
+    tn.add_argument("--prefix", dest="prefix", type=str, default="", help="Prefix for the trend tables. Default: ''")
+    tn.add_argument("--top", dest="top", type=int, default=100,
+                    help="Genes listed per trajectory and per fate in the csv tables; 0 lists all. Default: 100")
+    tn.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
     return parser
 
 
@@ -151,6 +170,15 @@ def main(argv=None):
                 sys.exit(2)
         from .silhouette import score
         score(args)
+    elif args.cmd_choice == "trends":
+        named = [(w, p) for w, p in (("trajectories", args.trajectories), ("fates", args.fates)) if p]
+        for what, path in [("counts", args.data)] + named:
+            if not _exists(path):
+                print(f"SpaDOT trends: the {what} does not exist: {path}. Please make sure it is correctly specified.",
+                      file=sys.stderr)
+                sys.exit(2)
+        from .trends import trends
+        trends(args)
     else:
         build_parser().print_help()
         sys.exit(2)
