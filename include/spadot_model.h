@@ -18,6 +18,7 @@
  *   spadot_pre_*, spadot_sparkx_*  utils/_utils.py:121-414 (SPARK-X) and utils/_preprocess_utils.py:11-49 (the preprocess stage)
  *   spadot_mk_*        no counterpart in the reference: scipy.stats.mannwhitneyu per (time point, gene, domain)
  *   spadot_silhouette  no counterpart in the reference: sklearn.metrics.silhouette_samples per (data set, labeling)
+ *   spadot_gmm_*       no counterpart in the reference: sklearn.mixture.GaussianMixture(covariance_type="full") per (data set, K)
  *   spadot_weighted_moments  no counterpart in the reference: X_csc.T @ W of the log-normalised counts, three moments
  */
 #ifndef SPADOT_MODEL_H
@@ -679,6 +680,39 @@ int spadot_mk_finish(const long long *r2, const long long *ties, const int *tp_o
  * (gridDim.y), n_max <= 2147483391 (int32 positions; n_max >= the n of every problem sizes gridDim.x). */
 int spadot_silhouette(const double *x, int d, int P, const long long *prob, const int *order, const int *coff, int n_max,
                       int k_min, int k_max, double *a, double *b, int *nearest, double *s, void *stream);
+
+/* ---------------------------------------------------------------- Gaussian mixtures (csrc/gmm.hip)
+ * EM for full-covariance Gaussian mixtures of P (data set, component count) problems at once, pinned to sklearn 1.7's
+ * GaussianMixture(covariance_type="full"): fp64, no atomics, every sum in a fixed order that depends on the problem alone (a
+ * problem gives the same bits alone, in any batch, run after run, for any grouping of iterations into calls).
+ * x: [rows, d] fp64, the CENTRED data sets one after the other.  prob[p, 4] int64: first row of the problem's set in x, first row of
+ * the problem in the per-point arrays (resp_init, norm, labels, resp, lp), n (points), K (components, 1 <= K <= K_max).
+ * With DP = 4 ceil(d / 4), T = DP (DP + 1) / 2, S = DP + T + 2, M = 1 + DP + T, nblk = ceil(n_max / 256):
+ *   par  [P, K_max, S]   mu_k (zero padding), then P_k = L_k^-T (Sigma_k = L_k L_k^T) packed by columns (P[a, j], a <= j, at
+ *                        j (j + 1) / 2 + a; identity padding), then sum_j log P_k[j, j], then log w_k -- stored per problem as the K_max means
+ *                        [K_max, DP] first and the K_max blocks of T + 2 doubles after them
+ *   w    [P, K_max]      w_k = nk / n;   cov [P, K_max, d, d]  Sigma_k;   mom [P, K_max, M] (may be null): sum r, sum r u_a,
+ *                        sum r u_a u_b (a <= b, packed like P) of the last M-step, u = x - the mean
+ *                        the iteration started from (resp_init: the raw moments, u = x, of its first pass)
+ *   part                 work space of P * nblk * (K_max * M + 1) doubles
+ *   done, n_iter [P] int32, lb [P] fp64: the stop flag, the iteration count and the lower bound (mean log-likelihood per
+ *                        point of the last E-step) of every problem; the caller starts them at 0, 0 and -inf
+ * spadot_gmm_em_step: if resp_init ([sum n, K_max] fp64, rows at the problem's offset) is not null, first one M-step from those
+ * responsibilities (nk = sum r + 10 eps, mu = sum r x / nk, Sigma = sum r (x - mu)(x - mu)^T / nk + reg_covar I, w = nk / n),
+ * in two passes over the points: raw moments for the means, then moments about those means.  Then
+ * `steps` iterations of E-step (lp_ik = (-(d log 2 pi + |(x_i - mu_k) P_k|^2) / 2 + log det P_k) + log w_k, norm_i =
+ * logsumexp_k lp_ik, r_ik = exp(lp_ik - norm_i)), M-step, and the stop rule: lb = mean norm, n_iter += 1, done = |lb - lb_prev|
+ * < tol (the M-step of the stopping iteration has been applied).  A problem whose done flag is set is left alone entirely.
+ * spadot_gmm_estep: one E-step with the parameters in par: norm [sum n], and where not null labels [sum n] int32 (argmax_k of
+ * lp - norm, first maximum), resp and lp [sum n, K_max].
+ * Return -22 for null or empty arguments and -7, before any launch, outside the limits: 1 <= d <= 32, 1 <= K_max <= 32,
+ * P <= 65535, n_max <= 2147483391 and 8 (max(K_max S, (K_max + 256) DP) + 256 (K_max | 1)) + 2048 <= 163840 bytes of LDS
+ * (d <= 24: K_max <= 32; d <= 28: K_max <= 29; d <= 32: K_max <= 24). */
+int spadot_gmm_em_step(const double *x, int d, int P, const long long *prob, int K_max, int n_max, double *par, double *w,
+                       double *cov, double *mom, const double *resp_init, double reg_covar, double tol, int steps, double *part,
+                       int *done, int *n_iter, double *lb, void *stream);
+int spadot_gmm_estep(const double *x, int d, int P, const long long *prob, int K_max, int n_max, const double *par, double *norm,
+                     int *labels, double *resp, double *lp, void *stream);
 
 /* ---------------------------------------------------------------- trends stage (csrc/trends.hip)
  * The log-normalised counts of every time point, transposed, times a dense row-major fp64 W[n, C] (rows in the permuted order of

@@ -275,6 +275,8 @@ def model_lib():
         "spadot_mk_finish": [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp],
         "spadot_silhouette": [vp, ci, ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp],
         "spadot_weighted_moments": [vp, vp, vp, vp, ci, ci, vp, ll, ci, vp, vp, vp, vp],
+        "spadot_gmm_em_step": [vp, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp, cd, cd, ci, vp, vp, vp, vp, vp],
+        "spadot_gmm_estep": [vp, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)

@@ -4,8 +4,11 @@ consecutive time points and its domain transition tables, and the plots.
 
 Arguments (the reference's): data, output_dir (default: the data file's directory), prefix ('adaptive_' when n_clusters is
 None and the prefix is empty), n_clusters (one k per time point, or None); added: device ('cuda:0'), write_tmaps (False),
-lineage (False), criterion ('elbow' | 'silhouette': how the adaptive mode picks k; 'silhouette' scores all 17 fits of every
-time point in one spadot_amd.silhouette.silhouette_many call and takes the k with the largest score).
+lineage (False), criterion ('elbow' | 'silhouette' | 'bic': how the adaptive mode picks k; 'silhouette' scores all 17 fits of
+every time point in one spadot_amd.silhouette.silhouette_many call and takes the k with the largest score), method
+('kmeans' | 'gmm': with 'gmm' every labeling of the K-means sweep starts one full-covariance Gaussian mixture, all of them in
+one spadot_amd.gmm.fit_sweep call; the domains are the mixtures' labels and every spot gets a membership probability per
+domain; the adaptive mode then picks k by 'bic' (the smallest BIC) or 'silhouette' (of the mixtures' labels)).
 
 Input: the latent.npz `train` always writes (X, rows, timepoint, spatial), latent.h5ad where `anndata` is importable, or an
 in-memory object with .X, .obs['timepoint'], .obsm['spatial'].  Time points are taken sorted; days are their positions.
@@ -19,6 +22,13 @@ Outputs in output_dir:
                                                .h5ad with the reference's names where anndata is importable
   {prefix}{tp}_WSS_vs_Clusters.png, {prefix}{tp}_domains.png, {prefix}transition_dotplot_{d}_{d+1}.png   (with matplotlib)
   {prefix}{tp}_silhouette_vs_Clusters.png      (criterion silhouette, with matplotlib)
+With method gmm (`kmeans` in domains.csv then holds the mixture's label: markers, score and trends read that name):
+  {prefix}{tp}_BIC.csv                         (adaptive) clusters, bic, aic, log_likelihood, n_iter, converged, selected
+  {prefix}{tp}_BIC_vs_Clusters.png             (adaptive, with matplotlib)
+  {prefix}memberships.npz                      X [N, sum_t K_t], rows, timepoint, names, in the layout of trajectories.npz: column
+                                               '<tp>_<domain>' holds the responsibilities of that time point's spots, 0 elsewhere
+                                               (`trends --trajectories` reads it: mean expression per soft domain)
+  {prefix}gmm.npz                              per time point tp: weights_{tp}, means_{tp}, covariances_{tp}; timepoints
 With lineage (spadot_amd.lineage: the plans of all pairs stay on the device and are chained, none is formed or solved twice):
   {prefix}transition_table_{d}_{e}.csv/.npz    for every e > d + 1: the long-range table, in the layout of the consecutive ones
                                                (.h5ad and transition_dotplot_{d}_{e}.png under the same conditions)
@@ -82,10 +92,18 @@ def validate(n_clusters, counts, d):
 
 def analyze(args):
     criterion = getattr(args, "criterion", "elbow") or "elbow"
-    if criterion not in ("elbow", "silhouette"):
-        raise ValueError(f"criterion must be 'elbow' or 'silhouette', not {criterion!r}")
-    if criterion == "silhouette" and getattr(args, "n_clusters", None) is not None:
-        raise ValueError("--criterion silhouette chooses the number of clusters: it cannot be combined with --n_clusters")
+    method = getattr(args, "method", "kmeans") or "kmeans"
+    if criterion not in ("elbow", "silhouette", "bic"):
+        raise ValueError(f"criterion must be 'elbow', 'silhouette' or 'bic', not {criterion!r}")
+    if method not in ("kmeans", "gmm"):
+        raise ValueError(f"method must be 'kmeans' or 'gmm', not {method!r}")
+    if criterion in ("silhouette", "bic") and getattr(args, "n_clusters", None) is not None:
+        raise ValueError(f"--criterion {criterion} chooses the number of clusters: it cannot be combined with --n_clusters")
+    if criterion == "bic" and method != "gmm":
+        raise ValueError("--criterion bic is the BIC of Gaussian mixtures: it needs --method gmm")
+    if method == "gmm" and criterion == "elbow" and getattr(args, "n_clusters", None) is None:
+        raise ValueError("adaptive --method gmm needs --criterion bic or silhouette: the elbow rule reads the WSS curve of "
+                         "K-means, and a mixture has no WSS")
     print("Loading latent representations...")
     adata, path = _utils.load_data(args.data)
     if not getattr(args, "output_dir", None):
@@ -108,6 +126,9 @@ def analyze(args):
     tps = sorted(set(tp_all.tolist()))
     masks = [tp_all == tp for tp in tps]
     ks = validate(n_clusters, {tp: int(m.sum()) for tp, m in zip(tps, masks)}, int(X.shape[1]))
+    if method == "gmm":
+        from .gmm import check_shape
+        check_shape(int(X.shape[1]), max(k for kt in ks for k in kt))
 
     import torch
     from . import analyze_ot, kmeans
@@ -122,18 +143,42 @@ def analyze(args):
     Xs = [torch.as_tensor(x, device=dev) for x in latents]
     adaptive = n_clusters is None
     by_silhouette = adaptive and criterion == "silhouette"
-    res = kmeans.fit_sweep(Xs, ks, random_state=1993, n_init=10, labels_for=None if adaptive and not by_silhouette else True)
+    use_gmm = method == "gmm"
+    res = kmeans.fit_sweep(Xs, ks, random_state=1993, n_init=10,
+                           labels_for=None if adaptive and not by_silhouette and not use_gmm else True)
+    mix = None
+    if use_gmm:                                           # every labeling of the sweep starts one mixture: one call
+        from . import gmm
+        t1 = time.perf_counter()
+        mix = gmm.fit_sweep(Xs, [[res[t][k].labels_ for k in ks[t]] for t in range(len(tps))], n_components=ks,
+                            resp_for=None if adaptive else True)
+        timings["gmm"] = time.perf_counter() - t1
     sil_scores = None
     if by_silhouette:                                     # all T x 17 labelings of the sweep: one launch
         from .silhouette import silhouette_many
         t1 = time.perf_counter()
-        sil = silhouette_many(Xs, [[res[t][k].labels_ for k in ADAPTIVE_KS] for t in range(len(tps))],
-                              n_clusters=[list(ADAPTIVE_KS) for _ in tps])
+        sil_labels = [[(mix[t][i].labels_ if use_gmm else res[t][k].labels_) for i, k in enumerate(ADAPTIVE_KS)]
+                      for t in range(len(tps))]
+        sil = silhouette_many(Xs, sil_labels, n_clusters=[list(ADAPTIVE_KS) for _ in tps])
         sil_scores = [[r.score for r in st] for st in sil]
         timings["silhouette"] = time.perf_counter() - t1      # the results are on the host: the launch has finished
-    chosen, labels, wss_tables, sil_tables = [], [], [], []
+    chosen, labels, wss_tables, sil_tables, bic_tables, models = [], [], [], [], [], []
     for t, tp in enumerate(tps):
-        if by_silhouette:
+        if use_gmm:
+            if not adaptive:
+                k, i = ks[t][0], 0
+            elif by_silhouette:
+                k = _analyze_utils.select_k_silhouette(sil_scores[t], timepoint=tp)
+                sil_tables.append(_analyze_utils.silhouette_table(sil_scores[t], k))
+                i = ADAPTIVE_KS.index(k)
+            else:
+                k = _analyze_utils.select_k_bic([m.bic_ for m in mix[t]], timepoint=tp)
+                i = ADAPTIVE_KS.index(k)
+            if adaptive:
+                bic_tables.append(_analyze_utils.bic_table(mix[t], k))
+            models.append(mix[t][i])
+            lab = mix[t][i].labels_
+        elif by_silhouette:
             wss = [res[t][k].inertia_ for k in ADAPTIVE_KS]
             k = _analyze_utils.select_k_silhouette(sil_scores[t], timepoint=tp)
             wss_tables.append(_analyze_utils.wss_table(wss, k))
@@ -150,6 +195,19 @@ def analyze(args):
             lab = res[t][k].labels_
         chosen.append(int(k))
         labels.append(np.asarray(lab, dtype=np.int64))
+    memberships = None
+    if use_gmm:
+        if adaptive:                                      # the responsibilities of the chosen mixtures: one E-step launch
+            from .gmm import estep_many
+            resp = [o[0]["resp"] for o in estep_many(Xs, [[m] for m in models], resp=True)]
+        else:
+            resp = [m.resp_ for m in models]
+        memberships = np.zeros((X.shape[0], int(sum(chosen))), dtype=np.float64)
+        c0 = 0
+        for m, r in zip(masks, resp):
+            memberships[m, c0:c0 + r.shape[1]] = r
+            c0 += r.shape[1]
+        member_names = np.array([f"{tp}_{c}" for tp, k in zip(tps, chosen) for c in range(k)])
     torch.cuda.synchronize(dev)
     timings["clustering"] = time.perf_counter() - t0
 
@@ -185,6 +243,15 @@ def analyze(args):
         tab.to_csv(os.path.join(out, prefix + str(tp) + "_WSS.csv"), index=False)
     for tp, tab in zip(tps, sil_tables):
         tab.to_csv(os.path.join(out, prefix + str(tp) + "_silhouette.csv"), index=False)
+    for tp, tab in zip(tps, bic_tables):
+        tab.to_csv(os.path.join(out, prefix + str(tp) + "_BIC.csv"), index=False)
+    if use_gmm:
+        np.savez_compressed(os.path.join(out, prefix + "memberships.npz"), X=memberships, rows=np.asarray(rows),
+                            timepoint=np.asarray(tp_all), names=member_names)
+        arrays = {"timepoints": np.asarray([str(tp) for tp in tps])}
+        for tp, m in zip(tps, models):
+            arrays.update({f"weights_{tp}": m.weights_, f"means_{tp}": m.means_, f"covariances_{tp}": m.covariances_})
+        np.savez_compressed(os.path.join(out, prefix + "gmm.npz"), **arrays)
     pairs = [(d, d + 1, tab) for d, tab in enumerate(tables)]
     if lin is not None:
         pairs += [(d, e, tab) for (d, e), tab in sorted(lin["long_tables"].items())]
@@ -199,7 +266,10 @@ def analyze(args):
         pass
     if _analyze_utils.have_matplotlib():
         for t, tp in enumerate(tps):
-            if adaptive:
+            if use_gmm and adaptive:
+                _analyze_utils.plot_bic(os.path.join(out, f"{prefix}{tp}_BIC_vs_Clusters.png"), ADAPTIVE_KS,
+                                        bic_tables[t]["bic"].tolist(), chosen[t])
+            if adaptive and not use_gmm:
                 _analyze_utils.plot_wss(os.path.join(out, f"{prefix}{tp}_WSS_vs_Clusters.png"), ADAPTIVE_KS,
                                         wss_tables[t]["wss"].tolist(), chosen[t])
             if by_silhouette:
@@ -218,6 +288,12 @@ def analyze(args):
     if by_silhouette:
         res["silhouette"] = dict(zip(tps, sil_scores))
         res["criterion"] = criterion
+    if use_gmm:
+        res["method"] = method
+        res["bic"] = dict(zip(tps, ([m.bic_ for m in mt] for mt in mix)))
+        res["memberships"] = {"X": memberships, "names": member_names, "rows": rows, "timepoint": tp_all}
+        if adaptive and not by_silhouette:
+            res["criterion"] = criterion
     if lin is not None:
         res["lineage"] = dict(lin, rows=rows, timepoint=tp_all)
     return res

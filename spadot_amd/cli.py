@@ -4,7 +4,7 @@
                                     [--gene_clusters kmeans|louvain] [--device cuda:0]
     python -m spadot_amd train   -i DATA [-o DIR] [--prefix P] [--config YAML] [--device cuda:0] [--save_model]
     python -m spadot_amd analyze -i LATENT [-o DIR] [--prefix P] [--n_clusters 5,7,7,6] [--device cuda:0] [--write_tmaps]
-                                 [--lineage] [--criterion elbow|silhouette]
+                                 [--lineage] [--criterion elbow|silhouette|bic] [--method kmeans|gmm]
     python -m spadot_amd markers -i COUNTS --domains CSV [-o DIR] [--prefix P] [--top 100] [--device cuda:0]
     python -m spadot_amd score   -i LATENT --domains CSV [-o DIR] [--prefix P] [--device cuda:0]
     python -m spadot_amd trends  -i COUNTS [--trajectories NPZ] [--fates NPZ] [-o DIR] [--prefix P] [--top 100] [--device cuda:0]
@@ -18,7 +18,10 @@ rank-sum test on the device (spadot_amd.markers).  `score` gives ever
 coefficient in the latent space and every domain and time point the mean; `analyze --criterion silhouette` picks the adaptive
 mode's k by the largest silhouette score instead of the elbow rule (spadot_amd.silhouette).  `trends` reads the
 trajectories.npz and / or fates.npz of `analyze --lineage` against the counts: the weighted mean expression of every gene along
-every domain's trajectory, and the correlation of every gene with every fate (spadot_amd.trends)."""
+every domain's trajectory, and the correlation of every gene with every fate (spadot_amd.trends).  `analyze --method
+gmm` refines every K-means labeling into a full-covariance Gaussian mixture on the device: elongated domains, a membership
+probability per spot (memberships.npz, which `trends --trajectories` reads as soft domains) and, with `--criterion bic`, the k of
+the smallest BIC (spadot_amd.gmm)."""
 import argparse
 import os
 import sys
@@ -77,10 +80,15 @@ def build_parser():
                     help="Also chain the transport plans across time points: transition tables between non-consecutive time "
                          "points, trajectories.npz (ancestors and descendants of every domain) and fates.npz (per spot, the "
                          "share of its mass that ends in each domain of the last time point).")
-    an.add_argument("--criterion", dest="criterion", choices=("elbow", "silhouette"), default="elbow",
-                    help="How the adaptive mode picks the number of clusters: the reference's elbow rule on the WSS curve, or "
-                         "the largest silhouette score of the fits (also writes {tp}_silhouette.csv). Not with --n_clusters. "
-                         "Default: elbow")
+    an.add_argument("--criterion", dest="criterion", choices=("elbow", "silhouette", "bic"), default="elbow",
+                    help="How the adaptive mode picks the number of clusters: the reference's elbow rule on the WSS curve, "
+                         "the largest silhouette score of the fits (also writes {tp}_silhouette.csv), or the smallest BIC of the "
+                         "Gaussian mixtures (needs --method gmm; writes {tp}_BIC.csv). Not with --n_clusters. Default: elbow")
+    an.add_argument("--method", dest="method", choices=("kmeans", "gmm"), default="kmeans",
+                    help="What a domain is: a K-means cluster, or a component of a full-covariance Gaussian mixture started "
+                         "from the K-means labels (elongated domains; also writes memberships.npz, the membership probability of "
+                         "every spot in every domain, and gmm.npz). The adaptive mode of gmm needs --criterion bic or silhouette. "
+                         "Default: kmeans")
 
     mk = sub.add_parser("markers", help="Marker genes of the spatial domains: per-domain Wilcoxon rank-sum tests of every gene.")
     mk.add_argument("-i", "--data", dest="data", type=str, required=True,

@@ -1858,6 +1858,44 @@ def silhouette_launch(X, prob, order, coff, n_max, k_min, k_max, out=None):
     return a, b, nearest, s
 
 
+GMM_LIMITS = ("1 <= d <= 32, 1 <= K <= 32, at most 65535 problems of at most 2147483391 points, and 8 (max(K S, (K + 256) DP) + "
+              "256 (K | 1)) + 2048 <= 163840 bytes of LDS with DP = 4 ceil(d / 4), S = DP + DP (DP + 1) / 2 + 2 (K = 32 up to "
+              "d = 24, K <= 29 up to d = 28, K <= 24 up to d = 32)")
+
+
+def gmm_em_steps(X, prob, n_max, par, w, cov, part, done, n_iter, lb, reg_covar, tol, steps, resp_init=None, mom=None):
+    """Gaussian-mixture EM for P problems (include/spadot_model.h: spadot_gmm_em_step): if resp_init is given, first the M-step
+    from those responsibilities; then `steps` iterations (E-step, M-step, stop rule), frozen problems left alone.  X [rows, d]
+    centred fp64; prob [P, 4] int64; par [P, K_max, S], w [P, K_max], cov [P, K_max, d, d], mom [P, K_max, M] or None, part (work
+    space), done / n_iter int32 [P], lb fp64 [P]: updated in place.  ValueError outside the limits, before any launch."""
+    _need_cuda(X, prob, par, w, cov, part, done, n_iter, lb, resp_init, mom)
+    if X.dtype != torch.float64 or not X.is_contiguous():
+        raise RuntimeError("gmm_em_steps takes a contiguous fp64 matrix")
+    P, K_max, d = int(prob.shape[0]), int(par.shape[1]), int(X.shape[1])
+    rc = model_lib().spadot_gmm_em_step(_p(X), d, P, _p(prob), K_max, int(n_max), _p(par), _p(w), _p(cov), _p(mom),
+                                        _p(resp_init), float(reg_covar), float(tol), int(steps), _p(part), _p(done), _p(n_iter),
+                                        _p(lb), _stream())
+    if rc == -7:
+        raise ValueError(f"spadot_gmm_em_step: outside its limits ({GMM_LIMITS}): d = {d}, K = {K_max}, {P} problems, "
+                         f"n <= {int(n_max)}")
+    _check(rc, "spadot_gmm_em_step")
+
+
+def gmm_estep(X, prob, n_max, par, norm, labels=None, resp=None, lp=None):
+    """One E-step of P problems with the parameters in par (spadot_gmm_estep): norm [sum n] fp64 and, where given, labels [sum n]
+    int32, resp and lp [sum n, K_max] fp64 are written.  ValueError outside the limits, before any launch."""
+    _need_cuda(X, prob, par, norm, labels, resp, lp)
+    if X.dtype != torch.float64 or not X.is_contiguous():
+        raise RuntimeError("gmm_estep takes a contiguous fp64 matrix")
+    P, K_max, d = int(prob.shape[0]), int(par.shape[1]), int(X.shape[1])
+    rc = model_lib().spadot_gmm_estep(_p(X), d, P, _p(prob), K_max, int(n_max), _p(par), _p(norm), _p(labels), _p(resp), _p(lp),
+                                      _stream())
+    if rc == -7:
+        raise ValueError(f"spadot_gmm_estep: outside its limits ({GMM_LIMITS}): d = {d}, K = {K_max}, {P} problems, "
+                         f"n <= {int(n_max)}")
+    _check(rc, "spadot_gmm_estep")
+
+
 # ----------------------------------------------------------------------------- optimiser
 
 def lloyd_steps(X, C, xoff, npts, n_max, rgroup, Kr, tol, done, inertia, part, steps, skip_done=False):

@@ -1,6 +1,6 @@
 """Host-side parts of the analyze stage: mirror of the reference's SpaDOT/utils/_analyze_utils.py.  The clustering itself
 runs on the device (spadot_amd.kmeans.fit_sweep); here are the elbow rule of Adaptive_clustering (:73-88) as a pure
-function, the silhouette rule of `--criterion silhouette` (no counterpart in the reference), the WSS table, and the plots (WSS curve :89-99, domains :140-164, transition dotplot :166-209), drawn with
+function, the silhouette rule of `--criterion silhouette` and the BIC rule of `--method gmm --criterion bic` (no counterparts in the reference), the WSS table, and the plots (WSS curve :89-99, domains :140-164, transition dotplot :166-209), drawn with
 matplotlib's object API on an Agg canvas (no pyplot: global plotting state is left alone; seaborn is not needed)."""
 import numpy as np
 
@@ -78,6 +78,32 @@ def silhouette_table(scores, selected, min_clusters=MIN_CLUSTERS):
     return pd.DataFrame({"clusters": ks, "silhouette": s, "selected": ks == int(selected)})
 
 
+def select_k_bic(bics, min_clusters=MIN_CLUSTERS, max_clusters=MAX_CLUSTERS, timepoint=None):
+    """The BIC rule of `analyze --method gmm --criterion bic`: bics[i] is the BIC of the mixture with k = min_clusters + i; the k
+    with the smallest BIC wins, on ties the first, NaN (a fit that broke down) is skipped.  ValueError naming the time point when
+    no BIC is defined."""
+    b = np.asarray(bics, dtype=np.float64).ravel()
+    if b.size != max_clusters - min_clusters + 1:
+        raise ValueError(f"select_k_bic needs one BIC per k = {min_clusters} .. {max_clusters} (got {b.size})")
+    ok = ~np.isnan(b)
+    if not ok.any():
+        where = f" at time point {timepoint}" if timepoint is not None else ""
+        raise ValueError(f"no mixture{where} has a defined BIC (k = {min_clusters} .. {max_clusters}); give the number of "
+                         f"clusters per time point with --n_clusters")
+    idx = np.flatnonzero(ok)
+    return int(min_clusters + idx[int(np.argmin(b[idx]))])            # first minimum
+
+
+def bic_table(fits, selected, min_clusters=MIN_CLUSTERS):
+    """The BIC table of one time point from its fitted mixtures (k ascending): columns clusters, bic, aic, log_likelihood, n_iter,
+    converged, selected (a pandas DataFrame)."""
+    import pandas as pd
+    ks = np.arange(min_clusters, min_clusters + len(fits))
+    return pd.DataFrame({"clusters": ks, "bic": [f.bic_ for f in fits], "aic": [f.aic_ for f in fits],
+                         "log_likelihood": [f.log_likelihood_ for f in fits], "n_iter": [f.n_iter_ for f in fits],
+                         "converged": [bool(f.converged_) for f in fits], "selected": ks == int(selected)})
+
+
 def have_matplotlib():
     try:
         import matplotlib  # noqa: F401
@@ -119,6 +145,21 @@ def plot_silhouette(path, clusters, scores, k_selected):
     ax.set_title("Silhouette score vs Number of Clusters")
     ax.set_xlabel("Number of Clusters")
     ax.set_ylabel("Silhouette score")
+    ax.set_xticks(clusters)
+    ax.grid()
+    fig.savefig(path)
+
+
+def plot_bic(path, clusters, bics, k_selected):
+    """{prefix}{tp}_BIC_vs_Clusters.png: the BIC of every k, the chosen one marked (as plot_wss)."""
+    clusters, bics = list(clusters), list(bics)
+    fig = _figure((10, 6))
+    ax = fig.add_subplot(1, 1, 1)
+    ax.plot(clusters, bics, marker="o")
+    ax.scatter(k_selected, bics[clusters.index(k_selected)], color="red", s=100, label="Selected Cluster")
+    ax.set_title("BIC vs Number of Clusters")
+    ax.set_xlabel("Number of Clusters")
+    ax.set_ylabel("BIC")
     ax.set_xticks(clusters)
     ax.grid()
     fig.savefig(path)
