@@ -20,6 +20,7 @@
  *   spadot_silhouette  no counterpart in the reference: sklearn.metrics.silhouette_samples per (data set, labeling)
  *   spadot_gmm_*       no counterpart in the reference: sklearn.mixture.GaussianMixture(covariance_type="full") per (data set, K)
  *   spadot_weighted_moments  no counterpart in the reference: X_csc.T @ W of the log-normalised counts, three moments
+ *   spadot_nhood_counts      no counterpart in the reference: the label-pair edge counts of squidpy's gr.nhood_enrichment
  */
 #ifndef SPADOT_MODEL_H
 #define SPADOT_MODEL_H
@@ -713,6 +714,27 @@ int spadot_gmm_em_step(const double *x, int d, int P, const long long *prob, int
                        int *done, int *n_iter, double *lb, void *stream);
 int spadot_gmm_estep(const double *x, int d, int P, const long long *prob, int K_max, int n_max, const double *par, double *norm,
                      int *labels, double *resp, double *lp, void *stream);
+
+/* ---------------------------------------------------------------- neighbourhood enrichment (csrc/nhood.hip)
+ * Count matrices C[a, b] = #{edges i -> j : lab[i] = a, lab[j] = b} of many (graph, labeling) problems in ONE launch: integers
+ * only, integer LDS atomics, no global atomics (a problem gives the same integers alone, in any batch, run after run).
+ * src, dst: int32 edge ends of the G graphs back to back (no self loops expected; duplicates are counted); labels: uint8, per
+ * graph either L labelings [L, n] (GIVEN) or one base labeling [n] (PERM).  desc [G, 12] int64, once in host memory (checked
+ * here) and once on the device (read by the kernel), per graph:
+ *   0 first edge   1 n   2 E   3 K   4 first label byte   5 L (labelings, or permutations)   6 first permutation index p0
+ *   (-1: GIVEN)   7 graph id g of the permutation keys   8 first output matrix (the sum of L over the graphs before; checked)
+ *   9 seed   10 the smallest and 11 the largest edge end of the graph (ignored where E = 0)
+ * PERM labeling l is base[pi(i)] with pi the permutation of (seed, g, p0 + l, n): a six-round balanced Feistel network on b
+ * bits (b = ceil(log2 n) rounded up to even, at least 2) with round function mix32(R ^ key_r) & mask, keys from splitmix64 of
+ * seed ^ (g << 32) ^ p, cycle-walked into 0 .. n-1 (tests/nhood_ref.py).
+ * out: int32 [sum L, K_max, K_max], matrix item0 + l of graph g in its top-left K x K corner, written completely (zeros too).
+ * A graph keeps its labeling in LDS where 16 K^2 + (n rounded up to 16) <= lds_limit (at most 163840; larger values mean
+ * 163840) and reads its labels from global memory otherwise.
+ * Return -22 for null or inconsistent arguments and -7, before any launch, outside the limits: 1 <= K <= K_max <= 32,
+ * 1 <= n <= 2147483647, E <= 2147483647, every edge end in 0 .. n-1, sum L <= 2147483647 (gridDim.x), p0 + L <= 2^32,
+ * g <= 2147483647.  A label >= K is the caller's to refuse (its edges are not counted). */
+int spadot_nhood_counts(const int *src, const int *dst, const unsigned char *labels, const long long *desc_host,
+                        const long long *desc_dev, int G, int K_max, long long lds_limit, int *out, void *stream);
 
 /* ---------------------------------------------------------------- trends stage (csrc/trends.hip)
  * The log-normalised counts of every time point, transposed, times a dense row-major fp64 W[n, C] (rows in the permuted order of

@@ -8,6 +8,7 @@
     python -m spadot_amd markers -i COUNTS --domains CSV [-o DIR] [--prefix P] [--top 100] [--device cuda:0]
     python -m spadot_amd score   -i LATENT --domains CSV [-o DIR] [--prefix P] [--device cuda:0]
     python -m spadot_amd trends  -i COUNTS [--trajectories NPZ] [--fates NPZ] [-o DIR] [--prefix P] [--top 100] [--device cuda:0]
+    python -m spadot_amd neighbors --domains CSV [-o DIR] [--prefix P] [--k 6] [--n_perms 1000] [--seed 0] [--device cuda:0]
 
 `preprocess` runs SPARK-X feature selection and the scaling on the device (spadot_amd.preprocess).  The balancing rule's gene
 clusters come from K-means by default; `--gene_clusters louvain` clusters SCTransform Pearson residuals with Louvain as the
@@ -21,7 +22,10 @@ trajectories.npz and / or fates.npz of `analyze --lineage` against the counts: t
 every domain's trajectory, and the correlation of every gene with every fate (spadot_amd.trends).  `analyze --method
 gmm` refines every K-means labeling into a full-covariance Gaussian mixture on the device: elongated domains, a membership
 probability per spot (memberships.npz, which `trends --trajectories` reads as soft domains) and, with `--criterion bic`, the k of
-the smallest BIC (spadot_amd.gmm)."""
+the smallest BIC (spadot_amd.gmm).  `neighbors` reads the spots' pixel coordinates in `analyze`'s domains.csv: on the
+k-nearest-neighbour graph of every time point, the neighbourhood-enrichment permutation test of every ordered pair of domains
+(counts, z-scores, empirical p-values), the share of every domain's neighbours per domain and of every spot's neighbours in its
+own domain (spadot_amd.neighbors)."""
 import argparse
 import os
 import sys
@@ -129,6 +133,19 @@ def build_parser():
     tn.add_argument("--top", dest="top", type=int, default=100,
                     help="Genes listed per trajectory and per fate in the csv tables; 0 lists all. Default: 100")
     tn.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
+
+    nb = sub.add_parser("neighbors", help="Neighbourhood enrichment of the spatial domains: which domains border which, on the "
+                                          "k-nearest-neighbour graph of every time point.")
+    nb.add_argument("--domains", dest="domains", type=str, required=True,
+                    help="The domains.csv written by analyze: row, timepoint, kmeans, pixel_x, pixel_y.")
+    nb.add_argument("-o", "--output_dir", dest="output_dir", type=str,
+                    help="Output directory. Default: the same as where the domains table locates.")
+    nb.add_argument("--prefix", dest="prefix", type=str, default="", help="Prefix for the enrichment tables. Default: ''")
+    nb.add_argument("--k", dest="k", type=int, default=6, help="Spatial neighbours per spot. Default: 6")
+    nb.add_argument("--n_perms", dest="n_perms", type=int, default=1000,
+                    help="Random relabelings (domain sizes kept) behind the z-scores and p-values. Default: 1000")
+    nb.add_argument("--seed", dest="seed", type=int, default=0, help="Seed of the relabelings. Default: 0")
+    nb.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
     return parser
 
 
@@ -187,6 +204,13 @@ def main(argv=None):
                 sys.exit(2)
         from .trends import trends
         trends(args)
+    elif args.cmd_choice == "neighbors":
+        if not _exists(args.domains):
+            print(f"SpaDOT neighbors: the domains table does not exist: {args.domains}. Please make sure it is correctly "
+                  "specified.", file=sys.stderr)
+            sys.exit(2)
+        from .neighbors import neighbors
+        neighbors(args)
     else:
         build_parser().print_help()
         sys.exit(2)

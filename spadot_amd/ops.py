@@ -1896,6 +1896,100 @@ def gmm_estep(X, prob, n_max, par, norm, labels=None, resp=None, lp=None):
     _check(rc, "spadot_gmm_estep")
 
 
+NHOOD_MAX_K = 32
+NHOOD_MAX = 2147483647             # nodes and edges of a graph (int32), and (graph, labeling) pairs of a call (gridDim.x)
+NHOOD_LDS_BYTES = 163840
+NHOOD_DESC = 12
+NHOOD_LIMITS = ("1 <= K <= 32, 1 <= n <= 2147483647 nodes and at most 2147483647 edges per graph, every edge end in 0 .. n-1, every "
+                "label below K, at most 2147483647 labelings per call, permutation indices below 2^32")
+
+
+def nhood_check(src, dst, labels, desc, K_max):
+    """The refusals of nhood_counts, before any launch: the limits from the descriptor, then the range of the edge ends and the
+    largest label of every graph by reductions on the device (one host round trip).  Returns the descriptor with columns 10 and
+    11 filled in; ValueError otherwise."""
+    import numpy as np
+    _need_cuda(src, dst, labels)
+    desc = np.array(desc, dtype=np.int64, order="C", copy=True)
+    if desc.ndim != 2 or desc.shape[1] != NHOOD_DESC or desc.shape[0] < 1:
+        raise ValueError(f"a descriptor holds {NHOOD_DESC} numbers per graph (got an array of shape {desc.shape})")
+    K_max = int(K_max)
+    if not 1 <= K_max <= NHOOD_MAX_K:
+        raise ValueError(f"spadot_nhood_counts takes 1 to {NHOOD_MAX_K} label values (got K_max = {K_max})")
+    items = 0
+    for g, (eoff, n, E, K, loff, L, p0, gid, item0, _seed, _lo, _hi) in enumerate(desc.tolist()):
+        if not 1 <= K <= K_max:
+            raise ValueError(f"graph {g} has {K} label values: spadot_nhood_counts takes 1 to {K_max} here, at most {NHOOD_MAX_K}")
+        if not 1 <= n <= NHOOD_MAX:
+            raise ValueError(f"graph {g} has {n} nodes: spadot_nhood_counts takes 1 to {NHOOD_MAX} (int32 node numbers)")
+        if not 0 <= E <= NHOOD_MAX:
+            raise ValueError(f"graph {g} has {E} edges: spadot_nhood_counts takes at most {NHOOD_MAX} per graph")
+        if L < 1 or item0 != items or eoff < 0 or loff < 0 or p0 < -1 or gid < 0:
+            raise ValueError(f"graph {g}: inconsistent descriptor {desc[g].tolist()}")
+        if p0 >= 0 and (p0 + L > 2 ** 32 or gid > NHOOD_MAX):
+            raise ValueError(f"graph {g}: permutation indices {p0} .. {p0 + L - 1} of graph id {gid}: the indices must stay below "
+                             f"2^32 and the graph id below 2^31")
+        items += L
+        if items > NHOOD_MAX:
+            raise ValueError(f"the call holds more than {NHOOD_MAX} labelings (the grid of one launch)")
+    for t, dt, what in ((src, torch.int32, "src"), (dst, torch.int32, "dst"), (labels, torch.uint8, "labels")):
+        if t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous 1-d {dt} tensor (got {tuple(t.shape)} {t.dtype})")
+    stats = []
+    for g, (eoff, n, E, K, loff, L, p0, *_rest) in enumerate(desc.tolist()):
+        nlab = n if p0 >= 0 else L * n
+        if eoff + E > src.numel() or eoff + E > dst.numel() or loff + nlab > labels.numel():
+            raise ValueError(f"graph {g}: its edges or labels reach past the end of the tensors")
+        if E > 0:
+            lo_s, hi_s = torch.aminmax(src[eoff:eoff + E])
+            lo_d, hi_d = torch.aminmax(dst[eoff:eoff + E])
+            stats += [torch.minimum(lo_s, lo_d).long(), torch.maximum(hi_s, hi_d).long()]
+        else:
+            stats += [torch.zeros((), dtype=torch.int64, device=labels.device)] * 2
+        stats.append(labels[loff:loff + nlab].max().long())
+    stats = torch.stack(stats).cpu().numpy().reshape(-1, 3)            # the one host round trip ahead of the launch
+    desc[:, 10], desc[:, 11] = stats[:, 0], stats[:, 1]
+    for g in range(desc.shape[0]):
+        n, E, K = (int(v) for v in desc[g, 1:4])
+        if E > 0 and (stats[g, 0] < 0 or stats[g, 1] >= n):
+            raise ValueError(f"graph {g} has edge ends {int(stats[g, 0])} .. {int(stats[g, 1])}: they must lie in 0 .. {n - 1}")
+        if stats[g, 2] >= K:
+            raise ValueError(f"graph {g} holds the label {int(stats[g, 2])}: labels must lie in 0 .. {K - 1}")
+    return desc
+
+
+def nhood_launch(src, dst, labels, desc, K_max, lds_limit=None, out=None, desc_dev=None):
+    """The launch of nhood_counts for a descriptor that nhood_check has returned (the library checks it again, on the host)."""
+    import numpy as np
+    _need_cuda(src, dst, labels, out, desc_dev)
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    K_max, items = int(K_max), int(desc[:, 5].sum())
+    lds_limit = NHOOD_LDS_BYTES if lds_limit is None else min(int(lds_limit), NHOOD_LDS_BYTES)
+    if lds_limit < 0:
+        raise ValueError(f"lds_limit is a number of bytes, 0 to {NHOOD_LDS_BYTES} (got {lds_limit})")
+    if out is None:
+        out = torch.empty((items, K_max, K_max), dtype=torch.int32, device=labels.device)
+    elif out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != items * K_max * K_max:
+        raise ValueError(f"out must be a contiguous int32 tensor of {items} x {K_max} x {K_max} values")
+    if desc_dev is None:
+        desc_dev = torch.as_tensor(desc, device=labels.device)
+    rc = model_lib().spadot_nhood_counts(_p(src), _p(dst), _p(labels), ctypes.c_void_p(desc.ctypes.data), _p(desc_dev),
+                                         int(desc.shape[0]), K_max, lds_limit, _p(out), _stream())
+    if rc == -7:
+        raise ValueError(f"spadot_nhood_counts: outside its limits ({NHOOD_LIMITS})")
+    _check(rc, "spadot_nhood_counts")
+    return out
+
+
+def nhood_counts(src, dst, labels, desc, K_max, lds_limit=None, out=None):
+    """Label-pair edge counts of many (graph, labeling) problems in ONE launch (include/spadot_model.h: spadot_nhood_counts).
+    src, dst int32 and labels uint8 device tensors, the graphs back to back; desc: int64 [G, 12] on the host as the header lays
+    it out (columns 10 and 11, the range of the edge ends, are filled in here).  lds_limit: the LDS bytes a workgroup may use
+    (default and at most 163840); a graph whose labels do not fit reads them from global memory.  Returns int32
+    [sum L, K_max, K_max] (out: the tensor to write into).  ValueError, before any launch, outside the limits."""
+    return nhood_launch(src, dst, labels, nhood_check(src, dst, labels, desc, K_max), K_max, lds_limit, out)
+
+
 # ----------------------------------------------------------------------------- optimiser
 
 def lloyd_steps(X, C, xoff, npts, n_max, rgroup, Kr, tol, done, inertia, part, steps, skip_done=False):

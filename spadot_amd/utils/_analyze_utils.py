@@ -184,6 +184,26 @@ def plot_domains(path, pixel_x, pixel_y, labels, timepoint):
     fig.savefig(path)
 
 
+def plot_nhood(path, zscore, timepoint):
+    """{prefix}{tp}_nhood.png: the neighbourhood-enrichment z-scores of one time point as a heat map (domain by neighbor), on
+    a diverging scale centred at 0; a cell without a z-score (no variance under permutation) stays blank."""
+    z = np.asarray(zscore, dtype=np.float64)
+    K = z.shape[0]
+    finite = z[np.isfinite(z)]
+    lim = float(np.abs(finite).max()) if finite.size and np.abs(finite).max() > 0 else 1.0
+    fig = _figure((max(4.0, 0.5 * K + 2.0), max(3.5, 0.5 * K + 1.5)))
+    ax = fig.add_subplot(1, 1, 1)
+    im = ax.imshow(np.ma.masked_invalid(z), cmap="RdBu_r", vmin=-lim, vmax=lim)
+    ax.set_xticks(range(K))
+    ax.set_yticks(range(K))
+    ax.set_xlabel("neighbor")
+    ax.set_ylabel("domain")
+    ax.set_title("Neighbourhood enrichment, time point: {}".format(timepoint))
+    fig.colorbar(im, label="z-score", ax=ax)
+    fig.tight_layout()
+    fig.savefig(path)
+
+
 def transition_min_prob(table):
     """Element-wise minimum of the column-normalised and the row-normalised transition table (_analyze_utils.py:184-194)."""
     t = np.asarray(table, dtype=np.float64)
