@@ -21,6 +21,7 @@
  *   spadot_gmm_*       no counterpart in the reference: sklearn.mixture.GaussianMixture(covariance_type="full") per (data set, K)
  *   spadot_weighted_moments  no counterpart in the reference: X_csc.T @ W of the log-normalised counts, three moments
  *   spadot_nhood_counts      no counterpart in the reference: the label-pair edge counts of squidpy's gr.nhood_enrichment
+ *   spadot_cooccur_counts    no counterpart in the reference: the label-pair counts by distance of squidpy's gr.co_occurrence
  */
 #ifndef SPADOT_MODEL_H
 #define SPADOT_MODEL_H
@@ -735,6 +736,27 @@ int spadot_gmm_estep(const double *x, int d, int P, const long long *prob, int K
  * g <= 2147483647.  A label >= K is the caller's to refuse (its edges are not counted). */
 int spadot_nhood_counts(const int *src, const int *dst, const unsigned char *labels, const long long *desc_host,
                         const long long *desc_dev, int G, int K_max, long long lds_limit, int *out, void *stream);
+
+/* ---------------------------------------------------------------- co-occurrence by distance (csrc/cooccur.hip)
+ * N[a, b, t] = #{ordered pairs (i, j), i != j : lab[i] = a, lab[j] = b, d2(i, j) <= r2[t]} of P (spot set, labeling,
+ * thresholds) problems in ONE counting launch, with d2 = fl(fl(dx dx) + fl(dy dy)), dx = x_i - x_j, dy = y_i - y_j: five
+ * correctly rounded fp64 operations, no fused multiply-add (what dx*dx + dy*dy <= r2 does in numpy; tests/cooccur_ref.py).  Two
+ * spots at the same coordinates are a pair at distance 0.  Integers only: register counters, 64-bit integer LDS and global adds
+ * onto the output, which the call zeroes itself (a problem gives the same integers alone, in any batch, run after run, under a
+ * larger K_max or B_max).  No n x n array, no floating-point sum.
+ * xy: fp64 [sum n, 2], per problem its spots ORDERED BY (label, index), the problems back to back.  desc [P, 40] int64, once in
+ * host memory (checked here) and once on the device (read by the kernel), per problem:
+ *   0 first spot in xy (the sum of n over the problems before; checked)   1 n   2 K   3 B
+ *   4 .. 4 + K   the cluster offsets: label k holds the sorted positions desc[4 + k] .. desc[5 + k] (desc[4] = 0, desc[4 + K] = n)
+ * r2 [P, BP] fp64 with BP = B_max rounded up to a multiple of 16, once in host memory (checked here) and once on the device: the
+ * problem's B squared thresholds, strictly increasing, finite and >= 0, then -1.0 in every padded place (no d2 is <= -1).
+ * out: int64 [P, K_max, K_max, B_max], problem p in its corner [K, K, B], written completely (zeros too).
+ * Return -22 for null or inconsistent arguments and -7, before any launch, outside the limits: 1 <= K <= K_max <= 32,
+ * 1 <= B <= B_max <= 64, 1 <= n <= 2147483391 (int32 positions of a 256-wide tile), P <= 65535 (gridDim.y), a threshold that is
+ * negative, not finite or not above the one before.  Non-finite coordinates and labels outside 0 .. K-1 are the caller's to
+ * refuse (the labels never reach the library: the offsets do). */
+int spadot_cooccur_counts(const double *xy, const long long *desc_host, const long long *desc_dev, const double *r2_host,
+                          const double *r2_dev, int P, int K_max, int B_max, long long *out, void *stream);
 
 /* ---------------------------------------------------------------- trends stage (csrc/trends.hip)
  * The log-normalised counts of every time point, transposed, times a dense row-major fp64 W[n, C] (rows in the permuted order of

@@ -9,6 +9,7 @@
     python -m spadot_amd score   -i LATENT --domains CSV [-o DIR] [--prefix P] [--device cuda:0]
     python -m spadot_amd trends  -i COUNTS [--trajectories NPZ] [--fates NPZ] [-o DIR] [--prefix P] [--top 100] [--device cuda:0]
     python -m spadot_amd neighbors --domains CSV [-o DIR] [--prefix P] [--k 6] [--n_perms 1000] [--seed 0] [--device cuda:0]
+    python -m spadot_amd cooccurrence --domains CSV [-o DIR] [--prefix P] [--bins 50] [--radius R] [--ring] [--device cuda:0]
 
 `preprocess` runs SPARK-X feature selection and the scaling on the device (spadot_amd.preprocess).  The balancing rule's gene
 clusters come from K-means by default; `--gene_clusters louvain` clusters SCTransform Pearson residuals with Louvain as the
@@ -25,7 +26,10 @@ probability per spot (memberships.npz, which `trends --trajectories` reads as so
 the smallest BIC (spadot_amd.gmm).  `neighbors` reads the spots' pixel coordinates in `analyze`'s domains.csv: on the
 k-nearest-neighbour graph of every time point, the neighbourhood-enrichment permutation test of every ordered pair of domains
 (counts, z-scores, empirical p-values), the share of every domain's neighbours per domain and of every spot's neighbours in its
-own domain (spadot_amd.neighbors)."""
+own domain (spadot_amd.neighbors).  `cooccurrence` reads the same table: for every time point, every ordered pair of
+domains and a ladder of radii up to a quarter of the tissue's diagonal (or `--radius`), the number of pairs of spots within that
+distance and the co-occurrence ratio, which tells how far an association reaches; `--ring` takes the pairs between consecutive
+radii instead of those within each (spadot_amd.cooccurrence)."""
 import argparse
 import os
 import sys
@@ -146,6 +150,22 @@ def build_parser():
                     help="Random relabelings (domain sizes kept) behind the z-scores and p-values. Default: 1000")
     nb.add_argument("--seed", dest="seed", type=int, default=0, help="Seed of the relabelings. Default: 0")
     nb.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
+
+    co = sub.add_parser("cooccurrence", help="Co-occurrence of the spatial domains by distance: for every pair of domains, how "
+                                             "many pairs of spots lie within each radius and the ratio to what the "
+                                             "domains' sizes alone would give.")
+    co.add_argument("--domains", dest="domains", type=str, required=True,
+                    help="The domains.csv written by analyze: row, timepoint, kmeans, pixel_x, pixel_y.")
+    co.add_argument("-o", "--output_dir", dest="output_dir", type=str,
+                    help="Output directory. Default: the same as where the domains table locates.")
+    co.add_argument("--prefix", dest="prefix", type=str, default="", help="Prefix for the co-occurrence tables. Default: ''")
+    co.add_argument("--bins", dest="bins", type=int, default=50, help="Radii per time point, 1 to 64. Default: 50")
+    co.add_argument("--radius", dest="radius", type=float,
+                    help="The largest radius, in the units of pixel_x / pixel_y. Default: per time point, a quarter of the "
+                         "diagonal of the spots' bounding box.")
+    co.add_argument("--ring", dest="ring", default=False, action="store_true",
+                    help="Ratios of the pairs between consecutive radii (annuli) instead of within each radius (discs).")
+    co.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
     return parser
 
 
@@ -211,6 +231,13 @@ def main(argv=None):
             sys.exit(2)
         from .neighbors import neighbors
         neighbors(args)
+    elif args.cmd_choice == "cooccurrence":
+        if not _exists(args.domains):
+            print(f"SpaDOT cooccurrence: the domains table does not exist: {args.domains}. Please make sure it is correctly "
+                  "specified.", file=sys.stderr)
+            sys.exit(2)
+        from .cooccurrence import cooccur
+        cooccur(args)
     else:
         build_parser().print_help()
         sys.exit(2)

@@ -1990,6 +1990,102 @@ def nhood_counts(src, dst, labels, desc, K_max, lds_limit=None, out=None):
     return nhood_launch(src, dst, labels, nhood_check(src, dst, labels, desc, K_max), K_max, lds_limit, out)
 
 
+COOCCUR_MAX_K = 32
+COOCCUR_MAX_B = 64
+COOCCUR_GRANULE = 16               # the thresholds of a problem are padded to a multiple of this with -1.0
+COOCCUR_MAX_N = 2147483391         # spots of a problem: int32 positions of a 256-wide tile (as spadot_silhouette)
+COOCCUR_MAX_P = 65535              # problems of a call (gridDim.y)
+COOCCUR_DESC = 40
+COOCCUR_LIMITS = ("1 <= K <= 32 label values, 1 <= B <= 64 thresholds that are finite, >= 0 and strictly increasing, "
+                  "1 <= n <= 2147483391 spots per problem, at most 65535 problems per call")
+
+
+def cooccur_padded(B_max):
+    """The threshold columns of a call whose largest problem has B_max thresholds."""
+    return (int(B_max) + COOCCUR_GRANULE - 1) // COOCCUR_GRANULE * COOCCUR_GRANULE
+
+
+def cooccur_check(xy, desc, r2, K_max, B_max):
+    """The refusals of cooccur_counts that the descriptor and the thresholds decide, before any launch.  Returns (desc int64
+    [P, 40], r2 fp64 [P, BP] padded with -1.0); ValueError otherwise.  r2: [P] sequences of squared thresholds, or the padded
+    array itself."""
+    import numpy as np
+    _need_cuda(xy)
+    desc = np.array(desc, dtype=np.int64, order="C", copy=True)
+    if desc.ndim != 2 or desc.shape[1] != COOCCUR_DESC or desc.shape[0] < 1:
+        raise ValueError(f"a descriptor holds {COOCCUR_DESC} numbers per problem (got an array of shape {desc.shape})")
+    K_max, B_max, P = int(K_max), int(B_max), desc.shape[0]
+    if not 1 <= K_max <= COOCCUR_MAX_K:
+        raise ValueError(f"spadot_cooccur_counts takes 1 to {COOCCUR_MAX_K} label values (got K_max = {K_max})")
+    if not 1 <= B_max <= COOCCUR_MAX_B:
+        raise ValueError(f"spadot_cooccur_counts takes 1 to {COOCCUR_MAX_B} thresholds (got B_max = {B_max})")
+    if P > COOCCUR_MAX_P:
+        raise ValueError(f"the call holds {P} problems: spadot_cooccur_counts takes at most {COOCCUR_MAX_P} (the grid of one "
+                         f"launch)")
+    if len(r2) != P:
+        raise ValueError(f"the call holds {P} problems and {len(r2)} sets of thresholds")
+    BP = cooccur_padded(B_max)
+    pad = np.full((P, BP), -1.0, dtype=np.float64)
+    first = 0
+    for p, row in enumerate(desc.tolist()):
+        off, n, K, B = row[:4]
+        if not 1 <= K <= K_max:
+            raise ValueError(f"problem {p} has {K} label values: spadot_cooccur_counts takes 1 to {K_max} here, at most "
+                             f"{COOCCUR_MAX_K}")
+        if not 1 <= B <= B_max:
+            raise ValueError(f"problem {p} has {B} thresholds: spadot_cooccur_counts takes 1 to {B_max} here, at most "
+                             f"{COOCCUR_MAX_B}")
+        if not 1 <= n <= COOCCUR_MAX_N:
+            raise ValueError(f"problem {p} has {n} spots: spadot_cooccur_counts takes 1 to {COOCCUR_MAX_N} (int32 positions)")
+        coff = row[4:5 + K]
+        if off != first or coff[0] != 0 or coff[-1] != n or any(hi < lo for lo, hi in zip(coff, coff[1:])):
+            raise ValueError(f"problem {p}: inconsistent descriptor {row[:5 + K]}")
+        first += n
+        t = np.asarray(r2[p], dtype=np.float64).reshape(-1)
+        if t.shape[0] == BP and np.all(t[B:] == -1.0):
+            t = t[:B]
+        if t.shape[0] != B:
+            raise ValueError(f"problem {p} has {t.shape[0]} thresholds and its descriptor says {B}")
+        if not np.all(np.isfinite(t)) or np.any(t < 0) or np.any(np.diff(t) <= 0):
+            raise ValueError(f"the squared thresholds of problem {p} must be finite, >= 0 and strictly increasing")
+        pad[p, :B] = t
+    if xy.dtype != torch.float64 or xy.dim() != 2 or xy.shape[1] != 2 or not xy.is_contiguous() or xy.shape[0] != first:
+        raise ValueError(f"xy must be a contiguous fp64 [{first}, 2] tensor (got {tuple(xy.shape)} {xy.dtype})")
+    return desc, pad
+
+
+def cooccur_launch(xy, desc, r2, K_max, B_max, out=None, desc_dev=None, r2_dev=None):
+    """The launch of cooccur_counts for what cooccur_check has returned (the library checks both again, on the host)."""
+    import numpy as np
+    _need_cuda(xy, out, desc_dev, r2_dev)
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    r2 = np.ascontiguousarray(r2, dtype=np.float64)
+    K_max, B_max, P = int(K_max), int(B_max), int(desc.shape[0])
+    if out is None:
+        out = torch.empty((P, K_max, K_max, B_max), dtype=torch.int64, device=xy.device)
+    elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != P * K_max * K_max * B_max:
+        raise ValueError(f"out must be a contiguous int64 tensor of {P} x {K_max} x {K_max} x {B_max} values")
+    if desc_dev is None:
+        desc_dev = torch.as_tensor(desc, device=xy.device)
+    if r2_dev is None:
+        r2_dev = torch.as_tensor(r2, device=xy.device)
+    rc = model_lib().spadot_cooccur_counts(_p(xy), ctypes.c_void_p(desc.ctypes.data), _p(desc_dev),
+                                           ctypes.c_void_p(r2.ctypes.data), _p(r2_dev), P, K_max, B_max, _p(out), _stream())
+    if rc == -7:
+        raise ValueError(f"spadot_cooccur_counts: outside its limits ({COOCCUR_LIMITS})")
+    _check(rc, "spadot_cooccur_counts")
+    return out
+
+
+def cooccur_counts(xy, desc, r2, K_max, B_max, out=None):
+    """Label-pair counts by distance of many problems in ONE counting launch (include/spadot_model.h: spadot_cooccur_counts).
+    xy: fp64 [sum n, 2] device tensor, per problem its spots ordered by (label, index), the problems back to back; desc: int64
+    [P, 40] on the host as the header lays it out; r2[p]: the squared thresholds of problem p.  Returns int64
+    [P, K_max, K_max, B_max] (out: the tensor to write into).  ValueError, before any launch, outside the limits."""
+    desc, pad = cooccur_check(xy, desc, r2, K_max, B_max)
+    return cooccur_launch(xy, desc, pad, K_max, B_max, out)
+
+
 # ----------------------------------------------------------------------------- optimiser
 
 def lloyd_steps(X, C, xoff, npts, n_max, rgroup, Kr, tol, done, inertia, part, steps, skip_done=False):

@@ -204,6 +204,32 @@ def plot_nhood(path, zscore, timepoint):
     fig.savefig(path)
 
 
+def plot_cooccurrence(path, radii, ratio, timepoint, ring=False):
+    """{prefix}{tp}_cooccurrence.png: one panel per domain, the co-occurrence ratio against the radius, one curve per
+    neighbor, a line at 1 (no association); a ratio that is not defined leaves a gap."""
+    import matplotlib
+    r = np.asarray(radii, dtype=np.float64)
+    v = np.asarray(ratio, dtype=np.float64)
+    K = v.shape[0]
+    cols = min(K, 4)
+    rows = (K + cols - 1) // cols
+    fig = _figure((3.6 * cols + 1.2, 2.8 * rows + 0.6))
+    cmap = matplotlib.colormaps["tab20"]
+    for a in range(K):
+        ax = fig.add_subplot(rows, cols, a + 1)
+        for b in range(K):
+            ax.plot(r, v[a, b], color=cmap(b % 20), linewidth=2.0 if a == b else 1.0, label=str(b))
+        ax.axhline(1.0, color="black", linewidth=0.8, linestyle="--")
+        ax.set_title("domain {}".format(a))
+        ax.set_xlabel("radius")
+        ax.set_ylabel("ratio")
+    handles, names = fig.axes[0].get_legend_handles_labels()
+    fig.legend(handles, names, title="neighbor", loc="center right")
+    fig.suptitle("Co-occurrence{}, time point: {}".format(" (rings)" if ring else "", timepoint))
+    fig.tight_layout(rect=(0, 0, 1 - 1.0 / (3.6 * cols + 1.2), 0.96))
+    fig.savefig(path)
+
+
 def transition_min_prob(table):
     """Element-wise minimum of the column-normalised and the row-normalised transition table (_analyze_utils.py:184-194)."""
     t = np.asarray(table, dtype=np.float64)
