@@ -22,6 +22,7 @@
  *   spadot_weighted_moments  no counterpart in the reference: X_csc.T @ W of the log-normalised counts, three moments
  *   spadot_nhood_counts      no counterpart in the reference: the label-pair edge counts of squidpy's gr.nhood_enrichment
  *   spadot_cooccur_counts    no counterpart in the reference: the label-pair counts by distance of squidpy's gr.co_occurrence
+ *   spadot_autocorr_sums     no counterpart in the reference: the edge sums of squidpy's gr.spatial_autocorr (Moran's I, Geary's C)
  */
 #ifndef SPADOT_MODEL_H
 #define SPADOT_MODEL_H
@@ -757,6 +758,39 @@ int spadot_nhood_counts(const int *src, const int *dst, const unsigned char *lab
  * refuse (the labels never reach the library: the offsets do). */
 int spadot_cooccur_counts(const double *xy, const long long *desc_host, const long long *desc_dev, const double *r2_host,
                           const double *r2_dev, int P, int K_max, int B_max, long long *out, void *stream);
+
+/* ---------------------------------------------------------------- spatial autocorrelation (csrc/autocorr.hip)
+ * The two edge sums behind Moran's I and Geary's C of every (time point, gene, labeling) in ONE launch.  Time point t is a
+ * directed edge list over its n spots (src, dst: int32 edge ends of the T time points back to back; no self loops expected,
+ * duplicates count) and the rows row0 .. row0 + n - 1 of a CSC matrix (colptr [G + 1] int64, ridx [nnz] int32 ascending inside
+ * a column, v [nnz] fp32: the layout of the preprocess, markers and trends stages).  Gene g of time point t has the value v of
+ * its stored entries and 0 elsewhere, and the centre c = centre[t * G + g] (fp64 [T, G], absolute gene index).  Labeling 0 (only
+ * with observed = 1) is the identity; the P labelings after it give spot i the value of spot pi_p(i), p = first .. first + P - 1,
+ * with pi_p the permutation of spadot_nhood_counts under (seed, graph id, p, n).  With x the labeled values promoted to fp64:
+ *   N[t, g - g0, l] = sum over edges i -> j of (x_i - c)(x_j - c)     D[t, g - g0, l] = sum over edges of (x_i - x_j)^2
+ * for the genes g0 .. g0 + ng - 1, fp64 [T, ng, observed + P], written completely.  One fp64 subtraction per centring and per
+ * difference, one fma per term; thread u of a workgroup adds the edges u, u + threads, ... in that order, the partial sums are
+ * added by shuffles inside the wavefront and across the wavefronts in wavefront order: no atomics, and the bits of a sum depend
+ * on the time point's edges, the gene's values, c, the labeling and `threads` alone (two runs, a gene alone, another batch,
+ * either path, either gs: the same bits).
+ * desc [T, 7] int64, once in host memory (checked here) and once on the device (read by the kernel), per time point:
+ *   0 first edge   1 n   2 E   3 row0   4 graph id of the permutation keys   5 the smallest and 6 the largest edge end (ignored
+ *   where E = 0)
+ * ridx_lo, ridx_hi: the smallest and the largest row index in ridx (ignored where nnz = 0).
+ * A workgroup handles one (time point, labeling, group of gs consecutive genes) and keeps a dense fp32 image [n, gs] of its
+ * labeled values in LDS where 2048 + 4 gs n <= lds_limit (at most 163840; larger values mean 163840); otherwise the image lives
+ * in scratch, fp32 [items, slab] with items = T (observed + P) ceil(ng / gs) and slab = the largest such gs n rounded up to a
+ * multiple of 4 (scratch_floats: how many floats scratch holds; scratch may be null where every image fits).
+ * threads: 256, 512 or 1024 (0: the default, 1024); gs: 2 or 4 (0: the default, 2).
+ * Return -22 for null, negative or inconsistent arguments (a scratch buffer that is too small among them) and -7, before any
+ * launch, outside the limits: 1 <= n <= 2147483647, E <= 2147483647, nnz <= 2147483647, every edge end in 0 .. n-1, every row
+ * index in 0 .. max(row0 + n) - 1, g0 + ng <= G, first + P <= 2^32, graph id <= 2147483647, items <= 2147483647 (gridDim.x),
+ * threads and gs as above. */
+int spadot_autocorr_sums(const int *src, const int *dst, const long long *colptr, const int *ridx, const float *v, long long nnz,
+                         long long ridx_lo, long long ridx_hi, const double *centre, const long long *desc_host,
+                         const long long *desc_dev, int T, int G, int g0, int ng, int observed, long long first, long long P,
+                         long long seed, long long lds_limit, float *scratch, long long scratch_floats, int threads, int gs,
+                         double *N, double *D, void *stream);
 
 /* ---------------------------------------------------------------- trends stage (csrc/trends.hip)
  * The log-normalised counts of every time point, transposed, times a dense row-major fp64 W[n, C] (rows in the permuted order of

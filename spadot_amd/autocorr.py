@@ -1,0 +1,342 @@
+"""The autocorr stage: which genes are spatially structured inside a time point, and how strongly.  On the spatial k-nearest-
+neighbour graph of every time point, Moran's I and Geary's C of every gene with an analytic and a permutation null (squidpy's
+gr.spatial_autocorr; csrc/autocorr.hip).  The reference has no such stage; the definition is restated in numpy in
+tests/autocorr_ref.py.
+
+    autocorr_sums(edges, dc, values, centre, n_perms)   the device primitive: N and D of every (time point, gene, labeling)
+    graph_moments(src, dst, n)                          S0, S1, S2 of a directed graph from integer torch ops on the device
+    autocorr_stats(N, D, n, E, m2, moments)             the host part: I, C, both nulls, BH
+    spatial_autocorr(edges, dc | dense, n_perms=100)    the test of every gene (or dense column) of every time point
+    autocorr(args)    the stage.  args: data, output_dir, prefix (''), k (6), n_perms (100), seed (0), top (100; 0 = all), device
+
+One time point: n spots, directed edges i -> j (no self loops; duplicates count; E of them), per gene the fp32 values v of
+trends.lognorm_values (0 where nothing is stored) promoted to fp64, and the centre c = the mean of v over the n spots.  Labeling 0
+is the identity; labeling 1 + p gives spot i the value x_i = v[pi_p(i)], pi_p the permutation of neighbors.py's docstring under
+(seed, index of the time point, p, n).  The device computes, in fp64 and a fixed order,
+    N[g, l] = sum over edges (x_i - c)(x_j - c),     D[g, l] = sum over edges (x_i - x_j)^2,
+and the host, with m2 = sum_i (v_i - c)^2 (from the fixed-order sums of trends.weighted_moments: S2 - S1^2 / n) and S0 = E,
+    I = n N / (S0 m2),     C = (n - 1) D / (2 S0 m2).
+A gene is degenerate in a time point if n < 3, E = 0 or m2 <= n 2^-50 sum v^2 (the rule of trends for a variance that cannot be
+told from zero): NaN in every statistic, left out of the BH family.
+Analytic null (normality; Cliff and Ord), a_ij the edge multiplicities: S1 = 1/2 sum_ij (a_ij + a_ji)^2, S2 = sum_i (outdeg_i +
+indeg_i)^2,
+    E[I] = -1 / (n - 1),  Var[I] = (n^2 S1 - n S2 + 3 S0^2) / (S0^2 (n^2 - 1)) - E[I]^2,
+    E[C] = 1,             Var[C] = ((2 S1 + S2)(n - 1) - 4 S0^2) / (2 (n + 1) S0^2),
+z_norm = (statistic - expectation) / sd, p_norm = 2 sf(|z_norm|) (NaN where the variance is not positive).
+Permutation null (P >= 1): mean and sd (ddof 0) of I_p and C_p give z_sim (NaN where sd = 0); on the device's own sums
+    p_sim_I = (1 + #{p : N_p >= N_0}) / (P + 1),     p_sim_C = (1 + #{p : D_p <= D_0}) / (P + 1)
+(one-sided towards positive autocorrelation); padj: Benjamini-Hochberg of p_sim over the non-degenerate genes of one time point
+(of p_norm with P = 0).
+
+The device sums; the host validates, takes the statistics and writes the files.  Limits: at most 2147483647 spots and edges per
+time point; permutation indices below 2^32."""
+import os
+import sys
+import time
+
+import numpy as np
+
+FIELDS = ("I", "C", "z_norm_I", "p_norm_I", "z_sim_I", "p_sim_I", "padj_I", "z_norm_C", "p_norm_C", "z_sim_C", "p_sim_C",
+          "padj_C", "mean", "pct")
+TABLE_COLUMNS = ("gene",) + FIELDS
+ARRAYS = FIELDS + ("N", "D", "m2")
+SCRATCH_FLOATS = 2 ** 28           # the images of one launch outside LDS: at most 1 GiB, the labelings are split beyond that
+
+
+class AutocorrResult:
+    """One time point: the fp64 statistics of the module docstring per gene (FIELDS, m2 [G]), the device's sums N, D [G, 1 + P]
+    (labeling 0 the observed one), n, E, the graph moments S0, S1, S2 and `degenerate` [G] bool."""
+
+    def __init__(self, N, D, n, E, mean, m2, sumsq, pct, moments):
+        self.N, self.D, self.n, self.E, self.mean, self.m2, self.pct = N, D, int(n), int(E), mean, m2, pct
+        self.S0, self.S1, self.S2 = (int(v) for v in moments)
+        for name, v in autocorr_stats(N, D, n, E, m2, moments, sumsq=sumsq).items():
+            setattr(self, name, v)
+
+
+def graph_moments(src, dst, n):
+    """S0 = E, S1 = 1/2 sum_ij (a_ij + a_ji)^2 and S2 = sum_i (outdeg_i + indeg_i)^2 of the directed graph src -> dst over n
+    nodes (a_ij the multiplicity of the edge i -> j), as Python integers: integer torch ops on the edges' device (unique on the
+    key i n + j of both orientations), no n x n array."""
+    import torch
+    if not isinstance(src, torch.Tensor) or not isinstance(dst, torch.Tensor) or not src.is_cuda or not dst.is_cuda:
+        raise RuntimeError("graph_moments takes the edges as device tensors; there is no CPU path")
+    n = int(n)
+    s, d = src.long(), dst.long()
+    E = int(s.numel())
+    if E == 0:
+        return 0, 0, 0
+    key = torch.cat([s * n + d, d * n + s])                  # a_ij + a_ji is the multiplicity of (i, j) in both orientations
+    _, w = torch.unique(key, return_counts=True)             # every unordered pair appears as (i, j) and as (j, i)
+    deg = torch.bincount(torch.cat([s, d]), minlength=n)
+    return E, int((w * w).sum().item()) // 2, int((deg * deg).sum().item())
+
+
+def autocorr_stats(N, D, n, E, m2, moments, sumsq=None):
+    """The host part of one time point (module docstring).  N, D: fp64 [G, 1 + P], labeling 0 the observed one; m2 [G];
+    moments = (S0, S1, S2); sumsq [G]: sum v^2 of the degeneracy rule (None: degenerate where m2 <= 0).  Returns a dict of fp64
+    [G] arrays (I, C and per statistic z_norm, p_norm, z_sim, p_sim, padj) and `degenerate` [G] bool."""
+    from scipy.special import ndtr
+    from .markers import bh_adjust
+    N, D, m2 = np.asarray(N, dtype=np.float64), np.asarray(D, dtype=np.float64), np.asarray(m2, dtype=np.float64)
+    G, P = N.shape[0], N.shape[1] - 1
+    n, E = int(n), int(E)
+    S0, S1, S2 = (float(v) for v in moments)
+    floor = np.zeros(G) if sumsq is None else n * 2.0 ** -50 * np.asarray(sumsq, dtype=np.float64)
+    bad = np.full(G, True) if n < 3 or E == 0 else ~(m2 > floor)
+    out = {"degenerate": bad}
+    safe = np.where(bad, 1.0, m2)[:, None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        stat = {"I": n * N / (max(S0, 1.0) * safe), "C": (n - 1.0) * D / (2.0 * max(S0, 1.0) * safe)}
+        if n >= 3 and E > 0:
+            EI = -1.0 / (n - 1.0)
+            null = {"I": (EI, (n * n * S1 - n * S2 + 3.0 * S0 * S0) / (S0 * S0 * (n * n - 1.0)) - EI * EI),
+                    "C": (1.0, ((2.0 * S1 + S2) * (n - 1.0) - 4.0 * S0 * S0) / (2.0 * (n + 1.0) * S0 * S0))}
+        else:
+            null = {"I": (np.nan, np.nan), "C": (np.nan, np.nan)}
+        for name, sums, tail in (("I", N, np.greater_equal), ("C", D, np.less_equal)):
+            obs, (mu, var) = stat[name][:, 0], null[name]
+            z = (obs - mu) / np.sqrt(var) if var > 0 else np.full(G, np.nan)
+            p_norm = 2.0 * ndtr(-np.abs(z))
+            if P >= 1:
+                sims = stat[name][:, 1:]
+                sd = sims.std(axis=1)
+                z_sim = np.where(sd > 0, (obs - sims.mean(axis=1)) / np.where(sd > 0, sd, 1.0), np.nan)
+                p_sim = (1.0 + tail(sums[:, 1:], sums[:, :1]).sum(axis=1)) / (P + 1.0)
+            else:
+                z_sim, p_sim = np.full(G, np.nan), np.full(G, np.nan)
+            base = p_sim if P >= 1 else p_norm
+            family = ~bad & np.isfinite(base)
+            padj = np.full(G, np.nan)
+            padj[family] = bh_adjust(base[family])
+            for key, v in ((name, obs), (f"z_norm_{name}", z), (f"p_norm_{name}", p_norm), (f"z_sim_{name}", z_sim),
+                           (f"p_sim_{name}", p_sim), (f"padj_{name}", padj)):
+                out[key] = np.where(bad, np.nan, v)
+    return out
+
+
+class _Csc:
+    """What autocorr_sums reads of a DeviceCounts, for data that is not one (the dense columns)."""
+
+    def __init__(self, colptr, ridx, tp_off_host, G, device):
+        self.colptr, self.ridx, self.tp_off_host, self.G, self.device = colptr, ridx, tp_off_host, int(G), device
+        self.T, self.n = len(tp_off_host) - 1, int(tp_off_host[-1])
+
+
+def _gene_range(genes, G):
+    if genes is None:
+        return 0, G
+    g0, g1 = (genes.start, genes.stop) if isinstance(genes, range) and genes.step == 1 else genes
+    g0, g1 = int(g0), int(g1)
+    if not 0 <= g0 < g1 <= G:
+        raise ValueError(f"genes must be a contiguous range inside the {G} genes (got {g0} .. {g1 - 1})")
+    return g0, g1 - g0
+
+
+def autocorr_sums(edges, dc, values, centre, n_perms, seed=0, first=0, observed=True, genes=None, lds_limit=None, out=None,
+                  threads=None, gs=None):
+    """N and D of every (time point, gene, labeling) (module docstring).  edges[t]: (src, dst) integer device tensors of time
+    point t, in the order of dc's time points; dc: a DeviceCounts (its colptr, ridx, tp_off); values: fp32 device tensor, one per
+    stored entry in CSC order; centre: fp64 [T, G] (device tensor or array).  Labelings: the identity first (observed), then the
+    permutations first .. first + n_perms - 1 under seed, time point t as graph index t.  genes: a contiguous range (range or
+    (start, stop)) of genes (default: all).  lds_limit: the LDS bytes a workgroup may use (default 163840): a time point whose
+    image does not fit (2048 + 8 n > lds_limit) keeps it in global memory, with the same bits.  One launch (several only where
+    the global-memory images of all labelings would pass 1 GiB).  Returns (N, D): [t] -> fp64 numpy [genes, labelings].
+    ValueError / RuntimeError before any launch; out: a pair of fp64 device tensors [T, genes, labelings] to write into."""
+    import torch
+    from . import ops
+    from .neighbors import _edge_pair
+    T, G = int(dc.T), int(dc.G)
+    if not edges or len(edges) != T:
+        raise ValueError(f"autocorr_sums takes one edge list per time point ({len(edges) if edges else 0} lists, {T} time points)")
+    pairs = [_edge_pair(e, dc.device, t) for t, e in enumerate(edges)]
+    if not isinstance(values, torch.Tensor):
+        raise RuntimeError("autocorr_sums takes the values as a device tensor (torch), not a host array")
+    centre = centre if isinstance(centre, torch.Tensor) else torch.as_tensor(np.asarray(centre, dtype=np.float64), device=dc.device)
+    g0, ng = _gene_range(genes, G)
+    n_perms, first, observed = int(n_perms), int(first), bool(observed)
+    if n_perms < 0:
+        raise ValueError(f"the number of permutations must not be negative (got n_perms = {n_perms})")
+    off = np.asarray(dc.tp_off_host, dtype=np.int64)
+    with torch.cuda.device(dc.device):
+        wide = [(t, torch.stack(torch.aminmax(torch.cat([s.reshape(-1), d.reshape(-1)]))).long()) for t, (s, d) in enumerate(pairs)
+                if s.dtype != torch.int32 and s.numel()]
+        if wide:                                             # the range is taken before the ends are narrowed to int32
+            for (t, _), (lo, hi) in zip(wide, torch.stack([w for _, w in wide]).cpu().tolist()):
+                if lo < 0 or hi >= off[t + 1] - off[t]:
+                    raise ValueError(f"time point {t} has edge ends {lo} .. {hi}: they must lie in 0 .. {int(off[t + 1] - off[t]) - 1}")
+        eoff = np.concatenate([[0], np.cumsum([int(s.shape[0]) for s, _ in pairs])]).astype(np.int64)
+        src = torch.cat([s.to(torch.int32) for s, _ in pairs]) if T > 1 else pairs[0][0].to(torch.int32).contiguous()
+        dst = torch.cat([d.to(torch.int32) for _, d in pairs]) if T > 1 else pairs[0][1].to(torch.int32).contiguous()
+        desc = np.zeros((T, ops.AUTOCORR_DESC), dtype=np.int64)
+        for t in range(T):
+            desc[t, :5] = (eoff[t], off[t + 1] - off[t], eoff[t + 1] - eoff[t], off[t], t)
+        args = (src, dst, dc.colptr, dc.ridx, values, centre.contiguous())
+        checked = ops.autocorr_check(*args, desc, g0, ng, observed, first, n_perms)
+        L = int(observed) + n_perms
+        per = ops.autocorr_scratch_floats(desc, ng, 1, lds_limit, gs)
+        step = L if per * L <= SCRATCH_FLOATS else max(1, SCRATCH_FLOATS // per)
+        if step >= L:
+            N, D = ops.autocorr_launch(*args, checked, g0, ng, observed, first, n_perms, seed, lds_limit, out, None, threads, gs)
+        else:                                                # the labelings in runs that share one scratch buffer
+            if out is not None:
+                raise ValueError("out is taken only by a call that is one launch")
+            scratch = torch.empty(per * step, dtype=torch.float32, device=dc.device)
+            parts, l = [], 0
+            while l < L:
+                take, obs = min(step, L - l), observed and l == 0
+                parts.append(ops.autocorr_launch(*args, checked, g0, ng, obs, first + (l - int(observed) if l else 0),
+                                                 take - int(obs), seed, lds_limit, None, scratch, threads, gs))
+                l += take
+            N, D = (torch.cat([p[i] for p in parts], dim=2) for i in range(2))
+        N, D = N.reshape(T, ng, L).cpu().numpy(), D.reshape(T, ng, L).cpu().numpy()
+    return [N[t] for t in range(T)], [D[t] for t in range(T)]
+
+
+def _dense_csc(dense, device):
+    """Per-graph dense [n, C] device tensors as one CSC with every entry stored: (a _Csc, its fp32 values)."""
+    import torch
+    if not dense or any(not isinstance(x, torch.Tensor) for x in dense):
+        raise RuntimeError("spatial_autocorr takes a DeviceCounts or one dense device tensor [n, C] per time point")
+    C = None
+    for t, x in enumerate(dense):
+        if not x.is_cuda:
+            raise RuntimeError("spadot_amd takes the autocorrelation on the MI355X only (got a CPU tensor); there is no CPU path")
+        if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1 or x.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"the columns of time point {t} must be a float32 or float64 tensor [n, C] (got {tuple(x.shape)} "
+                             f"{x.dtype})")
+        if C is not None and int(x.shape[1]) != C:
+            raise ValueError(f"every time point must hold the same {C} columns (time point {t}: {int(x.shape[1])})")
+        C = int(x.shape[1])
+    off = np.concatenate([[0], np.cumsum([int(x.shape[0]) for x in dense])]).astype(np.int64)
+    n = int(off[-1])
+    if n * C > 2 ** 31 - 1:
+        raise ValueError(f"{n} spots x {C} columns: the dense path stores every entry and takes at most {2 ** 31 - 1}")
+    X = torch.cat([x.to(device=device, dtype=torch.float32) for x in dense])                   # [n, C]
+    if not bool(torch.isfinite(X).all()):
+        raise ValueError("the dense columns hold entries that are not finite")
+    colptr = torch.arange(C + 1, dtype=torch.int64, device=device) * n
+    ridx = torch.arange(n, dtype=torch.int32, device=device).repeat(C)
+    return _Csc(colptr, ridx, off, C, device), X.t().contiguous().reshape(-1)
+
+
+def _moments(dc, values):
+    """Per (time point, gene): the stored count, sum v and sum v^2 in fp64, a fixed order (trends.weighted_moments with a
+    column of ones for a DeviceCounts)."""
+    import torch
+    if isinstance(dc, _Csc):                                 # every entry stored: the columns are rows of a [C, n] matrix
+        V = values.reshape(dc.G, dc.n).to(torch.float64)
+        off = dc.tp_off_host
+        S1 = torch.stack([V[:, int(off[t]):int(off[t + 1])].sum(1) for t in range(dc.T)])
+        S2 = torch.stack([(V[:, int(off[t]):int(off[t + 1])] ** 2).sum(1) for t in range(dc.T)])
+        S0 = torch.as_tensor(np.diff(off).astype(np.float64), device=dc.device)[:, None].expand(dc.T, dc.G)
+        return S0, S1, S2
+    from .trends import weighted_moments
+    S0, S1, S2 = weighted_moments(dc, values, torch.ones((dc.n, 1), dtype=torch.float64, device=dc.device))
+    return S0[:, :, 0], S1[:, :, 0], S2[:, :, 0]
+
+
+def spatial_autocorr(edges, data, values=None, n_perms=100, seed=0, lds_limit=None):
+    """Moran's I and Geary's C of every gene of every time point with both nulls (module docstring).  edges[t]: (src, dst) device
+    tensors of time point t (spatial_edges); data: a DeviceCounts (values: its fp32 values in CSC order, default
+    trends.lognorm_values) or, per time point, a dense float32 / float64 device tensor [n, C] of columns such as fates or
+    memberships, taken as fp32 and stored completely as a CSC for the same kernel.  The observed labeling and all n_perms
+    permutations of all time points are one call to the library; time point t permutes under (seed, t).  Returns [t] ->
+    AutocorrResult."""
+    import torch
+    n_perms = int(n_perms)
+    if n_perms < 0:
+        raise ValueError(f"the number of permutations must not be negative (got n_perms = {n_perms})")
+    if hasattr(data, "colptr"):
+        dc = data
+        if values is None:
+            from .trends import lognorm_values
+            values = lognorm_values(dc)
+    else:
+        if values is not None:
+            raise ValueError("values go with a DeviceCounts; dense columns are their own values")
+        dev = data[0].device if data and isinstance(data[0], torch.Tensor) else None
+        dc, values = _dense_csc(data, dev)
+    with torch.cuda.device(dc.device):
+        S0, S1, S2 = _moments(dc, values)
+        n_t = torch.as_tensor(np.diff(np.asarray(dc.tp_off_host)).astype(np.float64), device=dc.device)[:, None]
+        centre = (S1 / n_t).contiguous()
+        m2 = torch.clamp(S2 - S1 * S1 / n_t, min=0.0)
+        N, D = autocorr_sums(edges, dc, values, centre, n_perms, seed=seed, lds_limit=lds_limit)
+        moments = [graph_moments(s, d, int(n_t[t, 0].item())) for t, (s, d) in enumerate(edges)]
+        centre, m2, S2, pct = centre.cpu().numpy(), m2.cpu().numpy(), S2.cpu().numpy(), (S0 / n_t).cpu().numpy()
+    off = np.asarray(dc.tp_off_host, dtype=np.int64)
+    return [AutocorrResult(N[t], D[t], int(off[t + 1] - off[t]), moments[t][0], centre[t], m2[t], S2[t], pct[t], moments[t])
+            for t in range(dc.T)]
+
+
+def autocorr_table(r, genes, top=100):
+    """The rows of {prefix}autocorr_{tp}.csv: the `top` genes (0 = all) by I descending (NaN last), then gene column."""
+    import pandas as pd
+    G = r.I.shape[0]
+    order = np.lexsort((np.arange(G), -np.where(np.isnan(r.I), -np.inf, r.I)))
+    if top:
+        order = order[:top]
+    cols = {"gene": np.asarray(genes)[order]}
+    cols.update({name: getattr(r, name)[order] for name in FIELDS})
+    return pd.DataFrame(cols, columns=list(TABLE_COLUMNS))
+
+
+def autocorr(args):
+    """Reads args.data (counts, as the markers and trends stages: coordinates from obsm['spatial']), builds spatial_edges(.., k) of
+    every time point and runs one spatial_autocorr call.  Writes {prefix}autocorr_{tp}.csv (TABLE_COLUMNS; args.top rows by
+    descending I, 0 = all) and {prefix}autocorr.npz ('{tp}_{field}' for ARRAYS over all genes and '{tp}_S0/S1/S2', plus timepoints,
+    genes, k, n_perms, seed; pinned time stamps: two runs with one seed write the same bytes).  Returns {'tables', 'results' (per
+    time point), 'timepoints', 'timings'}."""
+    import torch
+    from .cooccurrence import _savez
+    from .markers import load_marker_counts
+    from .neighbors import spatial_edges
+    from .preprocess import DeviceCounts
+    from .trends import lognorm_values
+    t_start = time.perf_counter()
+    top = getattr(args, "top", 100)
+    top = 100 if top is None else int(top)
+    k, n_perms, seed = int(getattr(args, "k", 6)), int(getattr(args, "n_perms", 100)), int(getattr(args, "seed", 0))
+    if top < 0 or k < 1 or n_perms < 0:
+        raise ValueError(f"the autocorr stage takes top >= 0, k >= 1 and n_perms >= 0 (got top = {top}, k = {k}, n_perms = "
+                         f"{n_perms})")
+    device = getattr(args, "device", None) or "cuda:0"
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("spadot_amd takes the autocorrelation on the MI355X only (device 'cuda:N'); there is no CPU path")
+    raw, path = load_marker_counts(args.data)
+    if not getattr(args, "output_dir", None):
+        args.output_dir = os.path.dirname(path) if path else os.getcwd()
+    os.makedirs(args.output_dir, exist_ok=True)
+    prefix = getattr(args, "prefix", "") or ""
+    dc = DeviceCounts(raw, dev)
+    if not np.all(np.isfinite(dc.spatial)):
+        raise ValueError("the data holds spots without finite spatial coordinates")
+    tps = [str(t) for t in dc.tps]
+    off = dc.tp_off_host
+    t_read = time.perf_counter()
+    edges = [spatial_edges(dc.spatial[int(off[t]):int(off[t + 1])], k, dev) for t in range(dc.T)]
+    torch.cuda.synchronize(dev)
+    t_graph = time.perf_counter()
+    with torch.cuda.device(dev):
+        res = spatial_autocorr(edges, dc, lognorm_values(dc), n_perms=n_perms, seed=seed)
+    torch.cuda.synchronize(dev)
+    t_dev = time.perf_counter()
+    tables = {}
+    arrays = dict(timepoints=np.asarray(tps), genes=np.asarray(dc.genes).astype(str), k=np.int64(k), n_perms=np.int64(n_perms),
+                  seed=np.int64(seed))
+    for tp, r in zip(tps, res):
+        tables[tp] = autocorr_table(r, dc.genes, top)
+        tables[tp].to_csv(os.path.join(args.output_dir, f"{prefix}autocorr_{tp}.csv"), index=False)
+        for name in ARRAYS:
+            arrays[f"{tp}_{name}"] = getattr(r, name)
+        for name in ("S0", "S1", "S2"):
+            arrays[f"{tp}_{name}"] = np.int64(getattr(r, name))
+    _savez(os.path.join(args.output_dir, prefix + "autocorr.npz"), arrays)
+    t_end = time.perf_counter()
+    print(f"autocorr: {dc.G} genes x {dc.n} spots of {dc.T} time points, k = {k}, {n_perms} permutations, written to "
+          f"{args.output_dir}", file=sys.stderr)
+    return {"tables": tables, "results": dict(zip(tps, res)), "timepoints": tps,
+            "timings": dict(read_s=t_read - t_start, graph_s=t_graph - t_read, device_s=t_dev - t_graph, write_s=t_end - t_dev,
+                            total_s=t_end - t_start)}

@@ -10,6 +10,7 @@
     python -m spadot_amd trends  -i COUNTS [--trajectories NPZ] [--fates NPZ] [-o DIR] [--prefix P] [--top 100] [--device cuda:0]
     python -m spadot_amd neighbors --domains CSV [-o DIR] [--prefix P] [--k 6] [--n_perms 1000] [--seed 0] [--device cuda:0]
     python -m spadot_amd cooccurrence --domains CSV [-o DIR] [--prefix P] [--bins 50] [--radius R] [--ring] [--device cuda:0]
+    python -m spadot_amd autocorr -i COUNTS [-o DIR] [--prefix P] [--k 6] [--n_perms 100] [--seed 0] [--top 100] [--device cuda:0]
 
 `preprocess` runs SPARK-X feature selection and the scaling on the device (spadot_amd.preprocess).  The balancing rule's gene
 clusters come from K-means by default; `--gene_clusters louvain` clusters SCTransform Pearson residuals with Louvain as the
@@ -29,7 +30,10 @@ k-nearest-neighbour graph of every time point, the neighbourhood-enrichment perm
 own domain (spadot_amd.neighbors).  `cooccurrence` reads the same table: for every time point, every ordered pair of
 domains and a ladder of radii up to a quarter of the tissue's diagonal (or `--radius`), the number of pairs of spots within that
 distance and the co-occurrence ratio, which tells how far an association reaches; `--ring` takes the pairs between consecutive
-radii instead of those within each (spadot_amd.cooccurrence)."""
+radii instead of those within each (spadot_amd.cooccurrence).  `autocorr` reads the counts and their coordinates: on the
+k-nearest-neighbour graph of every time point, Moran's I and Geary's C of every gene with z-scores and p-values under the analytic
+(normality) null and under random relabelings of the spots: which genes are spatially structured inside a time point, how
+strongly, and with which sign (spadot_amd.autocorr)."""
 import argparse
 import os
 import sys
@@ -166,6 +170,22 @@ def build_parser():
     co.add_argument("--ring", dest="ring", default=False, action="store_true",
                     help="Ratios of the pairs between consecutive radii (annuli) instead of within each radius (discs).")
     co.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
+
+    ac = sub.add_parser("autocorr", help="Spatial autocorrelation of every gene inside every time point: Moran's I and Geary's C "
+                                         "on the k-nearest-neighbour graph, with an analytic and a permutation null.")
+    ac.add_argument("-i", "--data", dest="data", type=str, required=True,
+                    help="The counts: the .npz written by preprocess (its raw counts of the selected genes), or raw counts as "
+                         "preprocess reads them (.npz or .h5ad).")
+    ac.add_argument("-o", "--output_dir", dest="output_dir", type=str,
+                    help="Output directory. Default: the same as where the data locates.")
+    ac.add_argument("--prefix", dest="prefix", type=str, default="", help="Prefix for the autocorrelation tables. Default: ''")
+    ac.add_argument("--k", dest="k", type=int, default=6, help="Spatial neighbours per spot. Default: 6")
+    ac.add_argument("--n_perms", dest="n_perms", type=int, default=100,
+                    help="Random relabelings of the spots behind z_sim and p_sim; 0 leaves the analytic null alone. Default: 100")
+    ac.add_argument("--seed", dest="seed", type=int, default=0, help="Seed of the relabelings. Default: 0")
+    ac.add_argument("--top", dest="top", type=int, default=100,
+                    help="Genes listed per time point in the csv tables, by descending I; 0 lists all. Default: 100")
+    ac.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
     return parser
 
 
@@ -238,6 +258,13 @@ def main(argv=None):
             sys.exit(2)
         from .cooccurrence import cooccur
         cooccur(args)
+    elif args.cmd_choice == "autocorr":
+        if not _exists(args.data):
+            print(f"SpaDOT autocorr: the counts do not exist: {args.data}. Please make sure they are correctly specified.",
+                  file=sys.stderr)
+            sys.exit(2)
+        from .autocorr import autocorr
+        autocorr(args)
     else:
         build_parser().print_help()
         sys.exit(2)

@@ -2086,6 +2086,150 @@ def cooccur_counts(xy, desc, r2, K_max, B_max, out=None):
     return cooccur_launch(xy, desc, pad, K_max, B_max, out)
 
 
+AUTOCORR_DESC = 7
+AUTOCORR_MAX = 2147483647          # spots, edges and stored entries (int32), graph ids, and workgroups of a call (gridDim.x)
+AUTOCORR_LDS_BYTES = 163840
+AUTOCORR_LDS_FIXED = 2048          # LDS beside the image: the reduction and the segment bounds
+AUTOCORR_THREADS = 1024            # the library's defaults (Time)
+AUTOCORR_GS = 2
+AUTOCORR_LIMITS = ("1 <= n <= 2147483647 spots and at most 2147483647 edges per time point, at most 2147483647 stored entries, every "
+                   "edge end in 0 .. n-1, every row index inside the time points, permutation indices below 2^32, at most "
+                   "2147483647 workgroups per call, threads in (256, 512, 1024), gs in (2, 4)")
+
+
+def autocorr_check(src, dst, colptr, ridx, values, centre, desc, g0, ng, observed, first, P):
+    """The refusals of autocorr_sums, before any launch: the limits from the descriptor and the ranges, then the range of the
+    edge ends of every time point, the range of the row indices and the order of colptr by reductions on the device (one host
+    round trip).  Returns (the descriptor with columns 5 and 6 filled in, the smallest row index, the largest); ValueError
+    otherwise."""
+    import numpy as np
+    _need_cuda(src, dst, colptr, ridx, values, centre)
+    desc = np.array(desc, dtype=np.int64, order="C", copy=True)
+    if desc.ndim != 2 or desc.shape[1] != AUTOCORR_DESC or desc.shape[0] < 1:
+        raise ValueError(f"a descriptor holds {AUTOCORR_DESC} numbers per time point (got an array of shape {desc.shape})")
+    T = int(desc.shape[0])
+    g0, ng, first, P, observed = int(g0), int(ng), int(first), int(P), int(bool(observed))
+    for t, dt, what in ((src, torch.int32, "src"), (dst, torch.int32, "dst"), (ridx, torch.int32, "ridx"),
+                        (colptr, torch.int64, "colptr"), (values, torch.float32, "values"), (centre, torch.float64, "centre")):
+        if t.dtype != dt or not t.is_contiguous() or (t.dim() != 1 and what != "centre"):
+            raise ValueError(f"{what} must be a contiguous 1-d {dt} tensor (got {tuple(t.shape)} {t.dtype})")
+    G, nnz = int(colptr.numel()) - 1, int(ridx.numel())
+    if G < 1 or values.numel() != nnz or nnz > AUTOCORR_MAX:
+        raise ValueError(f"colptr holds {G} genes, ridx {nnz} and values {int(values.numel())} stored entries: at least one gene, "
+                         f"one value per entry and at most {AUTOCORR_MAX} entries")
+    if tuple(centre.shape) != (T, G):
+        raise ValueError(f"centre must be [T, G] = [{T}, {G}] (got {tuple(centre.shape)})")
+    if g0 < 0 or ng < 1 or g0 + ng > G:
+        raise ValueError(f"the genes {g0} .. {g0 + ng - 1} are not a range of the {G} genes")
+    if P < 0 or first < 0 or observed + P < 1:
+        raise ValueError(f"autocorr_sums takes P >= 0 permutations from first >= 0 on, and at least one labeling (got P = {P}, "
+                         f"first = {first}, observed = {bool(observed)})")
+    if first + P > 2 ** 32:
+        raise ValueError(f"permutation indices {first} .. {first + P - 1}: the indices must stay below 2^32")
+    rows = 0
+    for t, (eoff, n, E, row0, gid, _lo, _hi) in enumerate(desc.tolist()):
+        if not 1 <= n <= AUTOCORR_MAX:
+            raise ValueError(f"time point {t} has {n} spots: spadot_autocorr_sums takes 1 to {AUTOCORR_MAX} (int32 spot numbers)")
+        if not 0 <= E <= AUTOCORR_MAX:
+            raise ValueError(f"time point {t} has {E} edges: spadot_autocorr_sums takes at most {AUTOCORR_MAX} per time point")
+        if eoff < 0 or not 0 <= row0 <= AUTOCORR_MAX or not 0 <= gid <= AUTOCORR_MAX:
+            raise ValueError(f"time point {t}: inconsistent descriptor {desc[t].tolist()}")
+        if eoff + E > src.numel() or eoff + E > dst.numel():
+            raise ValueError(f"time point {t}: its edges reach past the end of the tensors")
+        rows = max(rows, row0 + n)
+    if T * (observed + P) * -(-ng // 2) > AUTOCORR_MAX:
+        raise ValueError(f"the call holds more than {AUTOCORR_MAX} workgroups (the grid of one launch)")
+    zero = torch.zeros((), dtype=torch.int64, device=colptr.device)
+    stats = []
+    for eoff, n, E, *_rest in desc.tolist():
+        if E > 0:
+            lo_s, hi_s = torch.aminmax(src[eoff:eoff + E])
+            lo_d, hi_d = torch.aminmax(dst[eoff:eoff + E])
+            stats += [torch.minimum(lo_s, lo_d).long(), torch.maximum(hi_s, hi_d).long()]
+        else:
+            stats += [zero, zero]
+    if nnz > 0:
+        lo_r, hi_r = torch.aminmax(ridx)
+        stats += [lo_r.long(), hi_r.long()]
+    else:
+        stats += [zero, zero]
+    stats += [colptr[0], colptr[-1], (colptr[1:] < colptr[:-1]).any().long()]
+    stats = torch.stack(stats).cpu().numpy()                             # the one host round trip ahead of the launch
+    ends = stats[:2 * T].reshape(T, 2)
+    desc[:, 5], desc[:, 6] = ends[:, 0], ends[:, 1]
+    for t in range(T):
+        n, E = int(desc[t, 1]), int(desc[t, 2])
+        if E > 0 and (ends[t, 0] < 0 or ends[t, 1] >= n):
+            raise ValueError(f"time point {t} has edge ends {int(ends[t, 0])} .. {int(ends[t, 1])}: they must lie in 0 .. {n - 1}")
+    ridx_lo, ridx_hi, c0, c1, unordered = (int(v) for v in stats[2 * T:])
+    if nnz > 0 and (ridx_lo < 0 or ridx_hi >= rows):
+        raise ValueError(f"ridx holds the row indices {ridx_lo} .. {ridx_hi}: they must lie in 0 .. {rows - 1}")
+    if c0 != 0 or c1 != nnz or unordered:
+        raise ValueError(f"colptr must ascend from 0 to the {nnz} stored entries (it runs from {c0} to {c1})")
+    return desc, ridx_lo, ridx_hi
+
+
+def autocorr_scratch_floats(desc, ng, L, lds_limit=None, gs=None):
+    """The floats of the scratch buffer of a call (0: every image fits in LDS), as the library computes it."""
+    gs = AUTOCORR_GS if not gs else int(gs)
+    lds_limit = AUTOCORR_LDS_BYTES if lds_limit is None else min(int(lds_limit), AUTOCORR_LDS_BYTES)
+    slab = max([(gs * int(n) + 3) & ~3 for n in desc[:, 1] if AUTOCORR_LDS_FIXED + 4 * gs * int(n) > lds_limit] or [0])
+    return slab * int(desc.shape[0]) * int(L) * -(-int(ng) // gs)
+
+
+def autocorr_launch(src, dst, colptr, ridx, values, centre, checked, g0, ng, observed, first, P, seed=0, lds_limit=None, out=None,
+                    scratch=None, threads=None, gs=None, desc_dev=None):
+    """The launch of autocorr_sums for what autocorr_check has returned (the library checks the descriptor again, on the host)."""
+    import numpy as np
+    desc, ridx_lo, ridx_hi = checked
+    _need_cuda(src, dst, colptr, ridx, values, centre, scratch, desc_dev, *(out or ()))
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    T, G, L = int(desc.shape[0]), int(colptr.numel()) - 1, int(bool(observed)) + int(P)
+    lds_limit = AUTOCORR_LDS_BYTES if lds_limit is None else min(int(lds_limit), AUTOCORR_LDS_BYTES)
+    if lds_limit < 0:
+        raise ValueError(f"lds_limit is a number of bytes, 0 to {AUTOCORR_LDS_BYTES} (got {lds_limit})")
+    threads, gs = int(threads or 0), int(gs or 0)
+    if threads not in (0, 256, 512, 1024) or gs not in (0, 2, 4):
+        raise ValueError(f"spadot_autocorr_sums: outside its limits ({AUTOCORR_LIMITS})")
+    dev = colptr.device
+    if out is None:
+        out = tuple(torch.empty((T, int(ng), L), dtype=torch.float64, device=dev) for _ in range(2))
+    elif len(out) != 2 or any(o.dtype != torch.float64 or not o.is_contiguous() or o.numel() != T * int(ng) * L for o in out):
+        raise ValueError(f"out must be two contiguous float64 tensors of {T} x {int(ng)} x {L} values")
+    need = autocorr_scratch_floats(desc, ng, L, lds_limit, gs)
+    if need and scratch is None:
+        scratch = torch.empty(need, dtype=torch.float32, device=dev)
+    elif need and (scratch.dtype != torch.float32 or not scratch.is_contiguous() or scratch.numel() < need):
+        raise ValueError(f"scratch must be a contiguous float32 tensor of at least {need} values")
+    if desc_dev is None:
+        desc_dev = torch.as_tensor(desc, device=dev)
+    seed = int(seed) & (2 ** 64 - 1)
+    rc = model_lib().spadot_autocorr_sums(_p(src), _p(dst), _p(colptr), _p(ridx), _p(values), int(ridx.numel()), ridx_lo, ridx_hi,
+                                          _p(centre), ctypes.c_void_p(desc.ctypes.data), _p(desc_dev), T, G, int(g0), int(ng),
+                                          int(bool(observed)), int(first), int(P), seed - 2 ** 64 if seed >= 2 ** 63 else seed,
+                                          lds_limit, _p(scratch) if need else None, int(scratch.numel()) if need else 0, threads,
+                                          gs, _p(out[0]), _p(out[1]), _stream())
+    if rc == -7:
+        raise ValueError(f"spadot_autocorr_sums: outside its limits ({AUTOCORR_LIMITS})")
+    _check(rc, "spadot_autocorr_sums")
+    return out
+
+
+def autocorr_sums(src, dst, colptr, ridx, values, centre, desc, g0, ng, observed, first, P, seed=0, lds_limit=None, out=None,
+                  scratch=None, threads=None, gs=None):
+    """The edge sums N and D behind Moran's I and Geary's C of every (time point, gene, labeling) in ONE launch
+    (include/spadot_model.h: spadot_autocorr_sums).  src, dst int32 edge ends of the time points back to back; colptr int64,
+    ridx int32 and values fp32: the CSC arrays of a DeviceCounts; centre fp64 [T, G]; desc: int64 [T, 7] on the host as the
+    header lays it out (columns 5 and 6, the range of the edge ends, are filled in here).  Labelings: the identity (observed)
+    and the permutations first .. first + P - 1 under seed.  lds_limit: the LDS bytes a workgroup may use (default and at most
+    163840); a time point whose image does not fit keeps it in `scratch` (allocated here when not given).  Returns (N, D), fp64
+    device tensors [T, ng, observed + P] (out: the pair to write into).  ValueError, before any launch, outside the limits;
+    RuntimeError for a CPU tensor."""
+    checked = autocorr_check(src, dst, colptr, ridx, values, centre, desc, g0, ng, observed, first, P)
+    return autocorr_launch(src, dst, colptr, ridx, values, centre, checked, g0, ng, observed, first, P, seed, lds_limit, out,
+                           scratch, threads, gs)
+
+
 # ----------------------------------------------------------------------------- optimiser
 
 def lloyd_steps(X, C, xoff, npts, n_max, rgroup, Kr, tol, done, inertia, part, steps, skip_done=False):
