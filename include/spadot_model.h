@@ -23,6 +23,7 @@
  *   spadot_nhood_counts      no counterpart in the reference: the label-pair edge counts of squidpy's gr.nhood_enrichment
  *   spadot_cooccur_counts    no counterpart in the reference: the label-pair counts by distance of squidpy's gr.co_occurrence
  *   spadot_autocorr_sums     no counterpart in the reference: the edge sums of squidpy's gr.spatial_autocorr (Moran's I, Geary's C)
+ *   spadot_ligrec_*          no counterpart in the reference: the per-domain sums and comparison counts of squidpy's gr.ligrec
  */
 #ifndef SPADOT_MODEL_H
 #define SPADOT_MODEL_H
@@ -791,6 +792,50 @@ int spadot_autocorr_sums(const int *src, const int *dst, const long long *colptr
                          const long long *desc_dev, int T, int G, int g0, int ng, int observed, long long first, long long P,
                          long long seed, long long lds_limit, float *scratch, long long scratch_floats, int threads, int gs,
                          double *N, double *D, void *stream);
+
+/* ---------------------------------------------------------------- ligand-receptor test (csrc/ligrec.hip)
+ * spadot_ligrec_sums: the per-domain expression sums of selected genes under the identity labeling and / or a run of
+ * permutations, for all time points in ONE launch.  Time point t is the rows row0 .. row0 + n - 1 of a CSC matrix (colptr
+ * [G + 1] int64, ridx [nnz] int32 ascending inside a column, v [nnz] fp32: the layout of the preprocess, markers and trends
+ * stages) and labels[row0 .. row0 + n - 1], one byte per row in 0 .. K-1 (label_hi: the largest byte in labels).  Labeling 0
+ * (only with observed = 1) is the label itself; the P labelings after it give spot i the label of spot pi_p(i), p = first ..
+ * first + P - 1, with pi_p the permutation of spadot_nhood_counts under (seed, graph id, p, n).  For the selected genes
+ * genes[0 .. ng-1] (int32, any order, repeats allowed; gene_lo, gene_hi: the smallest and the largest), with v promoted to fp64:
+ *   S[t, l, j, k] = sum of v over the stored entries of gene genes[j] in time point t whose row has label k under labeling l
+ * fp64 [T, observed + P, ng, K], written completely, and with observed = 1
+ *   cnt[t, j, k]  = the number of those entries with v > 0 under labeling 0                       int32 [T, ng, K].
+ * One workgroup per (time point, labeling, chunk of gc selected genes); a wavefront takes a gene at a time, lane u adds the
+ * entries u, u + 64, ... of the gene's segment in ascending order, the 64 lane sums are added by shuffles at offsets 32, 16,
+ * .. 1: no atomics, and the bits of a sum depend on the segment and the labels of its rows alone (two runs, a gene alone, any
+ * batch, any gc, either thread count, either path: the same bits).
+ * desc [T, 3] int64, once in host memory (checked here) and once on the device (read by the kernel), per time point:
+ *   0 n   1 row0   2 graph id of the permutation keys
+ * ridx_lo, ridx_hi: the smallest and the largest row index in ridx (ignored where nnz = 0).
+ * A workgroup keeps its accumulators in LDS (512 K threads / 64 bytes) and, where 512 K threads / 64 + n rounded up to 16 <=
+ * lds_limit (at most 163840; larger values mean 163840), the n label bytes of its labeling beside them; otherwise it evaluates
+ * pi_p per stored entry and reads the labels from global memory.
+ * threads: 256 or 512 (0: the default, 512); gc >= 1 (0: the default, 128).
+ * Return -22 for null, negative or inconsistent arguments (no labeling at all among them) and -7, before any launch, outside
+ * the limits: 1 <= K <= 32, label_hi < K, 1 <= n <= 2147483647, nnz <= 2147483647, every row index in 0 .. max(row0 + n) - 1,
+ * every selected gene in 0 .. G-1, first + P <= 2^32, graph id <= 2147483647, T (observed + P) ceil(ng / gc) <= 2147483647
+ * (gridDim.x), threads as above. */
+int spadot_ligrec_sums(const long long *colptr, const int *ridx, const float *v, long long nnz, long long ridx_lo,
+                       long long ridx_hi, const unsigned char *labels, int label_hi, const long long *desc_host,
+                       const long long *desc_dev, int T, int G, int K, const int *genes, int ng, int gene_lo, int gene_hi,
+                       int observed, long long first, long long P, long long seed, long long lds_limit, int threads, int gc,
+                       double *S, int *cnt, void *stream);
+
+/* spadot_ligrec_count: the comparisons behind the p-values, one launch.  S0 fp64 [T, ns, K]: the sums of labeling 0; S fp64
+ * [T, L, ns, K]: the sums of a run of L labelings, of which the first `skip` (0 or 1: the observed one) are not compared; wk
+ * fp64 [T, K]: 1 / n_k (0 for an empty domain); pairs int32 [M, 2]: (source, target) as positions in the ns selected genes
+ * (pair_lo, pair_hi: the smallest and the largest); mask uint8 [T, M, K, K]: the cells to test.  With
+ *   stat_l(m, a, b) = 0.5 * (S[t, l, src_m, a] * wk[t, a] + S[t, l, tgt_m, b] * wk[t, b])
+ * (two products and one sum, each rounded once: no fused multiply-add), every masked cell adds #{l >= skip : stat_l >= stat_0}
+ * to ge[t, m, a, b] (int32 [T, M, K, K]; the caller zeroes it; several runs accumulate exactly).  One workgroup per (time
+ * point, interaction), one thread per cell.
+ * Return -22 for null or inconsistent arguments and -7 outside the limits: K <= 32, T M <= 2147483647, pairs inside 0 .. ns-1. */
+int spadot_ligrec_count(const double *S0, const double *S, const double *wk, const int *pairs, int pair_lo, int pair_hi,
+                        const unsigned char *mask, int T, int M, int ns, int K, long long L, int skip, int *ge, void *stream);
 
 /* ---------------------------------------------------------------- trends stage (csrc/trends.hip)
  * The log-normalised counts of every time point, transposed, times a dense row-major fp64 W[n, C] (rows in the permuted order of

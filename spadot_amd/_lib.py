@@ -281,6 +281,9 @@ def model_lib():
         "spadot_cooccur_counts": [vp, vp, vp, vp, vp, ci, ci, ci, vp, vp],
         "spadot_autocorr_sums": [vp, vp, vp, vp, vp, ll, ll, ll, vp, vp, vp, ci, ci, ci, ci, ci, ll, ll, ll, ll, vp, ll, ci, ci,
                                  vp, vp, vp],
+        "spadot_ligrec_sums": [vp, vp, vp, ll, ll, ll, vp, ci, vp, vp, ci, ci, ci, vp, ci, ci, ci, ci, ll, ll, ll, ll, ci, ci, vp, vp,
+                               vp],
+        "spadot_ligrec_count": [vp, vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, ll, ci, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)

@@ -11,6 +11,8 @@
     python -m spadot_amd neighbors --domains CSV [-o DIR] [--prefix P] [--k 6] [--n_perms 1000] [--seed 0] [--device cuda:0]
     python -m spadot_amd cooccurrence --domains CSV [-o DIR] [--prefix P] [--bins 50] [--radius R] [--ring] [--device cuda:0]
     python -m spadot_amd autocorr -i COUNTS [-o DIR] [--prefix P] [--k 6] [--n_perms 100] [--seed 0] [--top 100] [--device cuda:0]
+    python -m spadot_amd ligrec  -i COUNTS --domains CSV --interactions CSV [-o DIR] [--prefix P] [--n_perms 1000] [--seed 0]
+                                 [--threshold 0.1] [--top 100] [--device cuda:0]
 
 `preprocess` runs SPARK-X feature selection and the scaling on the device (spadot_amd.preprocess).  The balancing rule's gene
 clusters come from K-means by default; `--gene_clusters louvain` clusters SCTransform Pearson residuals with Louvain as the
@@ -33,7 +35,10 @@ distance and the co-occurrence ratio, which tells how far an association reaches
 radii instead of those within each (spadot_amd.cooccurrence).  `autocorr` reads the counts and their coordinates: on the
 k-nearest-neighbour graph of every time point, Moran's I and Geary's C of every gene with z-scores and p-values under the analytic
 (normality) null and under random relabelings of the spots: which genes are spatially structured inside a time point, how
-strongly, and with which sign (spadot_amd.autocorr)."""
+strongly, and with which sign (spadot_amd.autocorr).  `ligrec` reads the counts, the domains table and a csv of
+ligand-receptor pairs (header `source,target`, gene names): for every time point, every pair and every ordered pair of domains, the
+mean expression of the ligand in the one domain and of the receptor in the other, with a p-value under random relabelings of the
+spots: which domains signal to which, and through which pair (spadot_amd.ligrec)."""
 import argparse
 import os
 import sys
@@ -186,6 +191,28 @@ def build_parser():
     ac.add_argument("--top", dest="top", type=int, default=100,
                     help="Genes listed per time point in the csv tables, by descending I; 0 lists all. Default: 100")
     ac.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
+
+    lr = sub.add_parser("ligrec", help="Ligand-receptor tests between the spatial domains of every time point: the mean expression "
+                                       "of every pair between every two domains, with a permutation null.")
+    lr.add_argument("-i", "--data", dest="data", type=str, required=True,
+                    help="The counts: the .npz written by preprocess (its raw counts of the selected genes), or raw counts as "
+                         "preprocess reads them (.npz or .h5ad).")
+    lr.add_argument("--domains", dest="domains", type=str, required=True,
+                    help="The domains.csv written by analyze: row, timepoint, kmeans.")
+    lr.add_argument("--interactions", dest="interactions", type=str, required=True,
+                    help="A csv with the header source,target: one ligand-receptor pair of gene names per row.")
+    lr.add_argument("-o", "--output_dir", dest="output_dir", type=str,
+                    help="Output directory. Default: the same as where the data locates.")
+    lr.add_argument("--prefix", dest="prefix", type=str, default="", help="Prefix for the ligand-receptor tables. Default: ''")
+    lr.add_argument("--n_perms", dest="n_perms", type=int, default=1000,
+                    help="Random relabelings of the spots (domain sizes kept) behind the p-values; 0 reports the means alone. "
+                         "Default: 1000")
+    lr.add_argument("--seed", dest="seed", type=int, default=0, help="Seed of the relabelings. Default: 0")
+    lr.add_argument("--threshold", dest="threshold", type=float, default=0.1,
+                    help="Share of a domain's spots that must express a gene for its cells to be tested. Default: 0.1")
+    lr.add_argument("--top", dest="top", type=int, default=100,
+                    help="Cells listed per time point in the csv tables, by ascending p-value; 0 lists all. Default: 100")
+    lr.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
     return parser
 
 
@@ -265,6 +292,14 @@ def main(argv=None):
             sys.exit(2)
         from .autocorr import autocorr
         autocorr(args)
+    elif args.cmd_choice == "ligrec":
+        for what, path in (("counts", args.data), ("domains table", args.domains), ("interactions table", args.interactions)):
+            if not _exists(path):
+                print(f"SpaDOT ligrec: the {what} does not exist: {path}. Please make sure it is correctly specified.",
+                      file=sys.stderr)
+                sys.exit(2)
+        from .ligrec import interactions
+        interactions(args)
     else:
         build_parser().print_help()
         sys.exit(2)

@@ -2230,6 +2230,152 @@ def autocorr_sums(src, dst, colptr, ridx, values, centre, desc, g0, ng, observed
                            scratch, threads, gs)
 
 
+LIGREC_DESC = 3
+LIGREC_MAX_K = 32
+LIGREC_MAX = 2147483647            # spots and stored entries (int32), graph ids, and workgroups of a call (gridDim.x)
+LIGREC_LDS_BYTES = 163840
+LIGREC_THREADS = 512               # the library's defaults (Time)
+LIGREC_GC = 128
+LIGREC_LIMITS = ("1 <= K <= 32 label values, every label below K, 1 <= n <= 2147483647 spots per time point, at most 2147483647 "
+                 "stored entries, every row index inside the time points, every selected gene inside the genes, permutation "
+                 "indices below 2^32, at most 2147483647 workgroups per call, threads in (256, 512), gene_chunk >= 1")
+
+
+def ligrec_lds_bytes(n, K, threads=None):
+    """The LDS bytes a workgroup needs to keep the labels of a time point of n spots beside its accumulators."""
+    return int(threads or LIGREC_THREADS) // 64 * int(K) * 512 + ((int(n) + 15) & ~15)
+
+
+def ligrec_check(colptr, ridx, values, labels, genes, desc, K, observed, first, P, gene_chunk=None):
+    """The refusals of ligrec_sums, before any launch: the limits from the descriptor and the ranges, then the range of the row
+    indices, of the labels and of the selected genes and the order of colptr by reductions on the device (one host round trip).
+    Returns (the descriptor, the smallest row index, the largest, the largest label, the smallest selected gene, the largest);
+    ValueError otherwise."""
+    import numpy as np
+    _need_cuda(colptr, ridx, values, labels, genes)
+    desc = np.array(desc, dtype=np.int64, order="C", copy=True)
+    if desc.ndim != 2 or desc.shape[1] != LIGREC_DESC or desc.shape[0] < 1:
+        raise ValueError(f"a descriptor holds {LIGREC_DESC} numbers per time point (got an array of shape {desc.shape})")
+    T, K = int(desc.shape[0]), int(K)
+    first, P, observed = int(first), int(P), int(bool(observed))
+    gc = LIGREC_GC if not gene_chunk else int(gene_chunk)
+    for t, dt, what in ((ridx, torch.int32, "ridx"), (colptr, torch.int64, "colptr"), (values, torch.float32, "values"),
+                        (labels, torch.uint8, "labels"), (genes, torch.int32, "genes")):
+        if t.dtype != dt or not t.is_contiguous() or t.dim() != 1:
+            raise ValueError(f"{what} must be a contiguous 1-d {dt} tensor (got {tuple(t.shape)} {t.dtype})")
+    if not 1 <= K <= LIGREC_MAX_K:
+        raise ValueError(f"spadot_ligrec_sums takes 1 to {LIGREC_MAX_K} label values (got K = {K})")
+    G, nnz, ng = int(colptr.numel()) - 1, int(ridx.numel()), int(genes.numel())
+    if G < 1 or values.numel() != nnz or nnz > LIGREC_MAX:
+        raise ValueError(f"colptr holds {G} genes, ridx {nnz} and values {int(values.numel())} stored entries: at least one gene, "
+                         f"one value per entry and at most {LIGREC_MAX} entries")
+    if ng < 1 or gc < 1:
+        raise ValueError(f"spadot_ligrec_sums takes at least one selected gene and gene_chunk >= 1 (got {ng} genes, gene_chunk = "
+                         f"{gc})")
+    if P < 0 or first < 0 or observed + P < 1:
+        raise ValueError(f"ligrec_sums takes P >= 0 permutations from first >= 0 on, and at least one labeling (got P = {P}, "
+                         f"first = {first}, observed = {bool(observed)})")
+    if first + P > 2 ** 32:
+        raise ValueError(f"permutation indices {first} .. {first + P - 1}: the indices must stay below 2^32")
+    rows = 0
+    for t, (n, row0, gid) in enumerate(desc.tolist()):
+        if not 1 <= n <= LIGREC_MAX:
+            raise ValueError(f"time point {t} has {n} spots: spadot_ligrec_sums takes 1 to {LIGREC_MAX} (int32 spot numbers)")
+        if not 0 <= row0 <= LIGREC_MAX or not 0 <= gid <= LIGREC_MAX:
+            raise ValueError(f"time point {t}: inconsistent descriptor {desc[t].tolist()}")
+        rows = max(rows, row0 + n)
+    if labels.numel() < rows:
+        raise ValueError(f"labels holds {int(labels.numel())} bytes: one per row of the time points, {rows}")
+    if T * (observed + P) * -(-ng // gc) > LIGREC_MAX:
+        raise ValueError(f"the call holds more than {LIGREC_MAX} workgroups (the grid of one launch)")
+    zero = torch.zeros((), dtype=torch.int64, device=colptr.device)
+    stats = list(torch.aminmax(ridx)) if nnz > 0 else [zero, zero]
+    stats += [labels[:rows].max(), *torch.aminmax(genes), colptr[0], colptr[-1], (colptr[1:] < colptr[:-1]).any()]
+    ridx_lo, ridx_hi, label_hi, gene_lo, gene_hi, c0, c1, unordered = (
+        int(v) for v in torch.stack([s.long() for s in stats]).cpu().numpy())                   # the one host round trip
+    if nnz > 0 and (ridx_lo < 0 or ridx_hi >= rows):
+        raise ValueError(f"ridx holds the row indices {ridx_lo} .. {ridx_hi}: they must lie in 0 .. {rows - 1}")
+    if label_hi >= K:
+        raise ValueError(f"labels holds the label {label_hi}: labels must lie in 0 .. {K - 1}")
+    if gene_lo < 0 or gene_hi >= G:
+        raise ValueError(f"the selected genes {gene_lo} .. {gene_hi} must lie in 0 .. {G - 1}")
+    if c0 != 0 or c1 != nnz or unordered:
+        raise ValueError(f"colptr must ascend from 0 to the {nnz} stored entries (it runs from {c0} to {c1})")
+    return desc, ridx_lo, ridx_hi, label_hi, gene_lo, gene_hi
+
+
+def ligrec_launch(colptr, ridx, values, labels, genes, checked, K, observed, first, P, seed=0, lds_limit=None, out=None,
+                  threads=None, gene_chunk=None, desc_dev=None):
+    """The launch of ligrec_sums for what ligrec_check has returned (the library checks the descriptor again, on the host)."""
+    import numpy as np
+    desc, ridx_lo, ridx_hi, label_hi, gene_lo, gene_hi = checked
+    _need_cuda(colptr, ridx, values, labels, genes, desc_dev, *(out or ()))
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    T, G, K, ng = int(desc.shape[0]), int(colptr.numel()) - 1, int(K), int(genes.numel())
+    observed, L = int(bool(observed)), int(bool(observed)) + int(P)
+    lds_limit = LIGREC_LDS_BYTES if lds_limit is None else min(int(lds_limit), LIGREC_LDS_BYTES)
+    if lds_limit < 0:
+        raise ValueError(f"lds_limit is a number of bytes, 0 to {LIGREC_LDS_BYTES} (got {lds_limit})")
+    threads, gc = int(threads or 0), int(gene_chunk or 0)
+    if threads not in (0, 256, 512) or gc < 0:
+        raise ValueError(f"spadot_ligrec_sums: outside its limits ({LIGREC_LIMITS})")
+    dev = colptr.device
+    if out is None:
+        out = (torch.empty((T, L, ng, K), dtype=torch.float64, device=dev),
+               torch.empty((T, ng, K), dtype=torch.int32, device=dev) if observed else None)
+    elif (len(out) != 2 or out[0].dtype != torch.float64 or not out[0].is_contiguous() or out[0].numel() != T * L * ng * K
+          or (observed and (out[1] is None or out[1].dtype != torch.int32 or not out[1].is_contiguous()
+                            or out[1].numel() != T * ng * K))):
+        raise ValueError(f"out must be a contiguous float64 tensor of {T} x {L} x {ng} x {K} values and, with the observed "
+                         f"labeling, a contiguous int32 tensor of {T} x {ng} x {K}")
+    if desc_dev is None:
+        desc_dev = torch.as_tensor(desc, device=dev)
+    seed = int(seed) & (2 ** 64 - 1)
+    rc = model_lib().spadot_ligrec_sums(_p(colptr), _p(ridx), _p(values), int(ridx.numel()), ridx_lo, ridx_hi, _p(labels), label_hi,
+                                        ctypes.c_void_p(desc.ctypes.data), _p(desc_dev), T, G, K, _p(genes), ng, gene_lo, gene_hi,
+                                        observed, int(first), int(P), seed - 2 ** 64 if seed >= 2 ** 63 else seed, lds_limit,
+                                        threads, gc, _p(out[0]), _p(out[1]) if observed else None, _stream())
+    if rc == -7:
+        raise ValueError(f"spadot_ligrec_sums: outside its limits ({LIGREC_LIMITS})")
+    _check(rc, "spadot_ligrec_sums")
+    return out
+
+
+def ligrec_sums(colptr, ridx, values, labels, genes, desc, K, observed, first, P, seed=0, lds_limit=None, out=None, threads=None,
+                gene_chunk=None):
+    """The per-domain expression sums of the selected genes of every (time point, labeling) in ONE launch
+    (include/spadot_model.h: spadot_ligrec_sums).  colptr int64, ridx int32 and values fp32: the CSC arrays of a DeviceCounts;
+    labels uint8, one per row; genes int32: the selected genes; desc: int64 [T, 3] on the host as the header lays it out.
+    Labelings: the labels themselves (observed) and the permutations first .. first + P - 1 under seed.  lds_limit: the LDS
+    bytes a workgroup may use (default and at most 163840); a time point whose labels do not fit beside the accumulators
+    permutes per stored entry.  Returns (S fp64 [T, observed + P, genes, K], c int32 [T, genes, K] or None without the observed
+    labeling) on the device (out: the pair to write into).  ValueError, before any launch, outside the limits; RuntimeError for a
+    CPU tensor."""
+    checked = ligrec_check(colptr, ridx, values, labels, genes, desc, K, observed, first, P, gene_chunk)
+    return ligrec_launch(colptr, ridx, values, labels, genes, checked, K, observed, first, P, seed, lds_limit, out, threads,
+                         gene_chunk)
+
+
+def ligrec_count(S0, S, wk, pairs, pair_range, mask, skip, ge):
+    """Adds, for every masked cell, the labelings l >= skip of the run S [T, L, ns, K] whose statistic is at least that of S0
+    [T, ns, K] into ge int32 [T, M, K, K] (include/spadot_model.h: spadot_ligrec_count).  wk fp64 [T, K]; pairs int32 [M, 2]
+    positions in the selected genes, pair_range their (smallest, largest); mask uint8 [T, M, K, K]."""
+    _need_cuda(S0, S, wk, pairs, mask, ge)
+    T, L, ns, K = (int(v) for v in S.shape)
+    M = int(pairs.shape[0])
+    for t, dt, shape, what in ((S0, torch.float64, (T, ns, K), "S0"), (S, torch.float64, (T, L, ns, K), "S"),
+                               (wk, torch.float64, (T, K), "wk"), (pairs, torch.int32, (M, 2), "pairs"),
+                               (mask, torch.uint8, (T, M, K, K), "mask"), (ge, torch.int32, (T, M, K, K), "ge")):
+        if t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise ValueError(f"{what} must be a contiguous {dt} tensor {shape} (got {tuple(t.shape)} {t.dtype})")
+    rc = model_lib().spadot_ligrec_count(_p(S0), _p(S), _p(wk), _p(pairs), int(pair_range[0]), int(pair_range[1]), _p(mask), T, M,
+                                         ns, K, L, int(skip), _p(ge), _stream())
+    if rc == -7:
+        raise ValueError(f"spadot_ligrec_count: outside its limits (K <= {LIGREC_MAX_K}, pairs inside the {ns} selected genes)")
+    _check(rc, "spadot_ligrec_count")
+    return ge
+
+
 # ----------------------------------------------------------------------------- optimiser
 
 def lloyd_steps(X, C, xoff, npts, n_max, rgroup, Kr, tol, done, inertia, part, steps, skip_done=False):
