@@ -36,6 +36,8 @@ import time
 
 import numpy as np
 
+from .utils._stage_utils import edge_pair, labeling_runs, savez_pinned
+
 FIELDS = ("I", "C", "z_norm_I", "p_norm_I", "z_sim_I", "p_sim_I", "padj_I", "z_norm_C", "p_norm_C", "z_sim_C", "p_sim_C",
           "padj_C", "mean", "pct")
 TABLE_COLUMNS = ("gene",) + FIELDS
@@ -144,12 +146,11 @@ def autocorr_sums(edges, dc, values, centre, n_perms, seed=0, first=0, observed=
     the global-memory images of all labelings would pass 1 GiB).  Returns (N, D): [t] -> fp64 numpy [genes, labelings].
     ValueError / RuntimeError before any launch; out: a pair of fp64 device tensors [T, genes, labelings] to write into."""
     import torch
-    from . import ops
-    from .neighbors import _edge_pair
+    from . import stage_ops as ops
     T, G = int(dc.T), int(dc.G)
     if not edges or len(edges) != T:
         raise ValueError(f"autocorr_sums takes one edge list per time point ({len(edges) if edges else 0} lists, {T} time points)")
-    pairs = [_edge_pair(e, dc.device, t) for t, e in enumerate(edges)]
+    pairs = [edge_pair(e, dc.device, t) for t, e in enumerate(edges)]
     if not isinstance(values, torch.Tensor):
         raise RuntimeError("autocorr_sums takes the values as a device tensor (torch), not a host array")
     centre = centre if isinstance(centre, torch.Tensor) else torch.as_tensor(np.asarray(centre, dtype=np.float64), device=dc.device)
@@ -175,19 +176,15 @@ def autocorr_sums(edges, dc, values, centre, n_perms, seed=0, first=0, observed=
         checked = ops.autocorr_check(*args, desc, g0, ng, observed, first, n_perms)
         L = int(observed) + n_perms
         per = ops.autocorr_scratch_floats(desc, ng, 1, lds_limit, gs)
-        step = L if per * L <= SCRATCH_FLOATS else max(1, SCRATCH_FLOATS // per)
-        if step >= L:
+        runs = labeling_runs(n_perms, observed, first, per, SCRATCH_FLOATS)
+        if len(runs) == 1:
             N, D = ops.autocorr_launch(*args, checked, g0, ng, observed, first, n_perms, seed, lds_limit, out, None, threads, gs)
         else:                                                # the labelings in runs that share one scratch buffer
             if out is not None:
                 raise ValueError("out is taken only by a call that is one launch")
-            scratch = torch.empty(per * step, dtype=torch.float32, device=dc.device)
-            parts, l = [], 0
-            while l < L:
-                take, obs = min(step, L - l), observed and l == 0
-                parts.append(ops.autocorr_launch(*args, checked, g0, ng, obs, first + (l - int(observed) if l else 0),
-                                                 take - int(obs), seed, lds_limit, None, scratch, threads, gs))
-                l += take
+            scratch = torch.empty(per * (runs[0][0] + runs[0][2]), dtype=torch.float32, device=dc.device)
+            parts = [ops.autocorr_launch(*args, checked, g0, ng, obs, p0, n, seed, lds_limit, None, scratch, threads, gs)
+                     for obs, p0, n in runs]
             N, D = (torch.cat([p[i] for p in parts], dim=2) for i in range(2))
         N, D = N.reshape(T, ng, L).cpu().numpy(), D.reshape(T, ng, L).cpu().numpy()
     return [N[t] for t in range(T)], [D[t] for t in range(T)]
@@ -289,7 +286,6 @@ def autocorr(args):
     genes, k, n_perms, seed; pinned time stamps: two runs with one seed write the same bytes).  Returns {'tables', 'results' (per
     time point), 'timepoints', 'timings'}."""
     import torch
-    from .cooccurrence import _savez
     from .markers import load_marker_counts
     from .neighbors import spatial_edges
     from .preprocess import DeviceCounts
@@ -333,7 +329,7 @@ def autocorr(args):
             arrays[f"{tp}_{name}"] = getattr(r, name)
         for name in ("S0", "S1", "S2"):
             arrays[f"{tp}_{name}"] = np.int64(getattr(r, name))
-    _savez(os.path.join(args.output_dir, prefix + "autocorr.npz"), arrays)
+    savez_pinned(os.path.join(args.output_dir, prefix + "autocorr.npz"), arrays)
     t_end = time.perf_counter()
     print(f"autocorr: {dc.G} genes x {dc.n} spots of {dc.T} time points, k = {k}, {n_perms} permutations, written to "
           f"{args.output_dir}", file=sys.stderr)

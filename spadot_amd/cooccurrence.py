@@ -27,9 +27,10 @@ The device counts; the host validates, takes the statistics and writes the files
 import os
 import sys
 import time
-import zipfile
 
 import numpy as np
+
+from .utils._stage_utils import savez_pinned
 
 MAX_CLUSTERS = 32
 MAX_BINS = 64
@@ -120,7 +121,7 @@ def cooccurrence_counts(coords, labels, radii=None, radii_sq=None, n_clusters=No
     its largest label + 1).  One call to the library for all problems; returns [g] -> int64 numpy [K, K, B].  ValueError /
     RuntimeError before any launch; out: an int64 device tensor [P, K_max, K_max, B_max] to write into."""
     import torch
-    from . import ops
+    from . import stage_ops as ops
     if (radii is None) == (radii_sq is None):
         raise ValueError("cooccurrence_counts takes exactly one of radii and radii_sq")
     given = radii if radii is not None else radii_sq
@@ -218,15 +219,6 @@ def cooccurrence_table(r):
                          "ratio": r.ratio.reshape(-1)}, columns=list(TABLE_COLUMNS))
 
 
-def _savez(path, arrays):
-    """np.savez with the archive's time stamps pinned, so that two runs write the same bytes (np.load reads it as any npz)."""
-    with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED, allowZip64=True) as z:
-        for name, v in arrays.items():
-            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
-            with z.open(info, "w", force_zip64=True) as f:
-                np.lib.format.write_array(f, np.asanyarray(v), allow_pickle=False)
-
-
 def cooccur(args):
     """Reads args.domains (the domains.csv of analyze: row, timepoint, kmeans, pixel_x, pixel_y) and counts every time point in
     one call.  Radii per time point: default_radii(.., bins), or args.radius * (1 .. bins) / bins.  Writes
@@ -281,7 +273,7 @@ def cooccur(args):
         tables[tp].to_csv(os.path.join(args.output_dir, f"{prefix}cooccurrence_{tp}.csv"), index=False)
         for name in ARRAYS:
             arrays[f"{tp}_{name}"] = getattr(r, name)
-    _savez(os.path.join(args.output_dir, prefix + "cooccurrence.npz"), arrays)
+    savez_pinned(os.path.join(args.output_dir, prefix + "cooccurrence.npz"), arrays)
     if _analyze_utils.have_matplotlib():
         for tp, r in zip(tps, res):
             _analyze_utils.plot_cooccurrence(os.path.join(args.output_dir, f"{prefix}{tp}_cooccurrence.png"), r.radii, r.ratio,

@@ -46,7 +46,7 @@ def check_shape(d, K):
     """ValueError unless the kernels take K components in d dimensions: the parameters of the problem (K S doubles, S = DP +
     DP (DP + 1) / 2 + 2, DP = 4 ceil(d / 4)) or its means and the block's 256 points ((K + 256) DP), and the 256 x (K | 1) tile of
     responsibilities, share one compute unit's LDS."""
-    from .ops import GMM_LIMITS
+    from .stage_ops import GMM_LIMITS
     if not (1 <= d <= MAX_DIM and 1 <= K <= MAX_COMPONENTS and lds_bytes(d, K) <= LDS_BYTES):
         raise ValueError(f"{K} components in {d} dimensions are outside the limits of the device Gaussian mixture: {GMM_LIMITS}")
 
@@ -134,7 +134,7 @@ class _Batch:
 
     def em(self, steps, reg_covar, tol, resp_init=None):
         import torch
-        from .ops import gmm_em_steps
+        from .stage_ops import gmm_em_steps
         with torch.cuda.device(self.dev):
             gmm_em_steps(self.X, self.prob, self.n_max, self.par, self.w, self.cov, self.part, self.done, self.n_iter, self.lb,
                          reg_covar, tol, steps, resp_init=resp_init, mom=self.mom)
@@ -142,7 +142,7 @@ class _Batch:
     def estep(self, labels=True, resp=False, lp=False):
         """(norm [total], labels [total] | None, resp [total, K_max] | None, lp | None), device tensors."""
         import torch
-        from .ops import gmm_estep
+        from .stage_ops import gmm_estep
         f64 = torch.float64
         with torch.cuda.device(self.dev):
             norm = torch.empty(self.total, dtype=f64, device=self.dev)

@@ -35,6 +35,8 @@ import time
 
 import numpy as np
 
+from .utils._stage_utils import labeling_runs, savez_pinned
+
 FIELDS = ("mean", "pvalue", "padj", "gene_mean", "gene_pct", "sizes", "tested", "ge")
 TABLE_COLUMNS = ("source", "target", "domain_source", "domain_target", "mean", "pvalue", "padj", "mean_source", "mean_target",
                  "pct_source", "pct_target")
@@ -90,7 +92,7 @@ def ligrec_stats(S0, ge, c, sizes, pairs, n_perms, threshold):
 def _device_args(dc, values, labels, genes, K):
     """The prepared tensors of a launch: (colptr, ridx, values, labels uint8, genes int32), desc int64 [T, 3] and K."""
     import torch
-    from . import ops
+    from . import stage_ops as ops
     if not isinstance(values, torch.Tensor):
         raise RuntimeError("ligrec_sums takes the values as a device tensor (torch), not a host array")
     dev = dc.device
@@ -119,12 +121,6 @@ def _device_args(dc, values, labels, genes, K):
     return (dc.colptr, dc.ridx, values, labels.contiguous(), genes.contiguous()), desc, int(K)
 
 
-def _runs(L, per, observed):
-    """The labelings of a call in runs whose sums fit SUMS_BYTES: [(first labeling, labelings, holds the observed one)]."""
-    step = L if per * L <= SUMS_BYTES else max(1, SUMS_BYTES // per)
-    return [(l, min(step, L - l), bool(observed) and l == 0) for l in range(0, L, step)]
-
-
 def ligrec_sums(dc, values, labels, genes, n_perms, seed=0, first=0, observed=True, lds_limit=None, gene_chunk=None, out=None,
                 threads=None, K=None):
     """S and c of every (time point, labeling, selected gene, domain) (module docstring).  dc: a DeviceCounts (its colptr, ridx,
@@ -138,7 +134,7 @@ def ligrec_sums(dc, values, labels, genes, n_perms, seed=0, first=0, observed=Tr
     observed labeling).  ValueError / RuntimeError before any launch; out: a pair of device tensors (fp64 [T, labelings, genes,
     K], int32 [T, genes, K]) to write into."""
     import torch
-    from . import ops
+    from . import stage_ops as ops
     n_perms, first, observed = int(n_perms), int(first), bool(observed)
     if n_perms < 0:
         raise ValueError(f"the number of permutations must not be negative (got n_perms = {n_perms})")
@@ -146,20 +142,20 @@ def ligrec_sums(dc, values, labels, genes, n_perms, seed=0, first=0, observed=Tr
         args, desc, K = _device_args(dc, values, labels, genes, K)
         checked = ops.ligrec_check(*args, desc, K, observed, first, n_perms, gene_chunk)
         T, ng, L = int(dc.T), int(args[4].numel()), int(observed) + n_perms
-        runs = _runs(L, 8 * T * ng * K, observed)
+        runs = labeling_runs(n_perms, observed, first, 8 * T * ng * K, SUMS_BYTES)
         if len(runs) == 1:
             S, c = ops.ligrec_launch(*args, checked, K, observed, first, n_perms, seed, lds_limit, out, threads, gene_chunk)
             S, c = S.reshape(T, L, ng, K).cpu().numpy(), (c.reshape(T, ng, K).cpu().numpy() if observed else None)
         else:                                                # the labelings in runs that share one buffer
             if out is not None:
                 raise ValueError("out is taken only by a call that is one launch")
-            buf = torch.empty(T * runs[0][1] * ng * K, dtype=torch.float64, device=dc.device)
+            buf = torch.empty(T * (runs[0][0] + runs[0][2]) * ng * K, dtype=torch.float64, device=dc.device)
             cnt = torch.empty((T, ng, K), dtype=torch.int32, device=dc.device) if observed else None
             parts, c = [], None
-            for l, take, obs in runs:
-                view = buf[:T * take * ng * K].view(T, take, ng, K)
-                ops.ligrec_launch(*args, checked, K, obs, first + (l - int(observed) if l else 0), take - int(obs), seed,
-                                  lds_limit, (view, cnt if obs else None), threads, gene_chunk)
+            for obs, p0, n in runs:
+                view = buf[:T * (obs + n) * ng * K].view(T, obs + n, ng, K)
+                ops.ligrec_launch(*args, checked, K, obs, p0, n, seed, lds_limit, (view, cnt if obs else None), threads,
+                                  gene_chunk)
                 parts.append(view.to("cpu", copy=True).numpy())
                 if obs:
                     c = cnt.cpu().numpy()
@@ -195,7 +191,7 @@ def ligrec(counts, labels, interactions, n_perms=1000, seed=0, threshold=0.1, de
     [M, K_t, K_t] with K_t the domains of the time point.  timings: a dict that receives the device milliseconds of the
     launches."""
     import torch
-    from . import ops
+    from . import stage_ops as ops
     from .markers import check_labels
     from .preprocess import DeviceCounts
     from .trends import lognorm_values
@@ -236,17 +232,16 @@ def ligrec(counts, labels, interactions, n_perms=1000, seed=0, threshold=0.1, de
         args, desc, K = _device_args(dc, values, lab, sel, K)
         checked = ops.ligrec_check(*args, desc, K, True, 0, n_perms, gene_chunk)
         dev = dc.device
-        runs = _runs(1 + n_perms, 8 * T * ns * K, True)
-        buf = torch.empty(T * runs[0][1] * ns * K, dtype=torch.float64, device=dev)
+        runs = labeling_runs(n_perms, True, 0, 8 * T * ns * K, SUMS_BYTES)
+        buf = torch.empty(T * (runs[0][0] + runs[0][2]) * ns * K, dtype=torch.float64, device=dev)
         cnt = torch.empty((T, ns, K), dtype=torch.int32, device=dev)
         ge = torch.zeros((T, M, K, K), dtype=torch.int32, device=dev)
         pairs_dev = torch.as_tensor(pairs.astype(np.int32), device=dev)
         S0 = wk = mask = None
-        for l, take, obs in runs:
-            view = buf[:T * take * ns * K].view(T, take, ns, K)
+        for obs, p0, n in runs:
+            view = buf[:T * (obs + n) * ns * K].view(T, obs + n, ns, K)
             stamp()
-            ops.ligrec_launch(*args, checked, K, obs, l - 1 if l else 0, take - int(obs), seed, lds_limit,
-                              (view, cnt if obs else None), threads, gene_chunk)
+            ops.ligrec_launch(*args, checked, K, obs, p0, n, seed, lds_limit, (view, cnt if obs else None), threads, gene_chunk)
             stamp()
             if obs:                                          # the observed sums, once: the mask is the host's
                 S0 = view[:, 0].clone()                      # its own buffer: the runs after this one reuse `buf`
@@ -254,7 +249,7 @@ def ligrec(counts, labels, interactions, n_perms=1000, seed=0, threshold=0.1, de
                 parts = [_tested(S0_host[t], c_host[t], sizes[t], pairs, threshold) for t in range(T)]
                 wk = torch.as_tensor(np.stack([p[2] for p in parts]), device=dev)
                 mask = torch.as_tensor(np.stack([p[4] for p in parts]).astype(np.uint8), device=dev)
-            if take - int(obs) > 0:
+            if n > 0:
                 stamp()
                 ops.ligrec_count(S0, view, wk, pairs_dev, (int(pairs.min()), int(pairs.max())), mask, int(obs), ge)
                 stamp()
@@ -322,7 +317,6 @@ def interactions(args):
     stamps: two runs with one seed write the same bytes).  Returns {'tables', 'results' (per time point), 'timepoints',
     'timings'}."""
     import torch
-    from .cooccurrence import _savez
     from .markers import load_marker_counts, read_domains
     from .preprocess import DeviceCounts
     t_start = time.perf_counter()
@@ -362,7 +356,7 @@ def interactions(args):
         tables[tp].to_csv(os.path.join(args.output_dir, f"{prefix}ligrec_{tp}.csv"), index=False)
         for name in FIELDS:
             arrays[f"{tp}_{name}"] = getattr(r, name)
-    _savez(os.path.join(args.output_dir, prefix + "ligrec.npz"), arrays)
+    savez_pinned(os.path.join(args.output_dir, prefix + "ligrec.npz"), arrays)
     t_end = time.perf_counter()
     print(f"ligrec: {pairs.shape[0]} interactions over {res[0].genes.shape[0]} genes x {dc.n} spots of {dc.T} time points, "
           f"{n_perms} permutations, written to {args.output_dir}", file=sys.stderr)

@@ -23,6 +23,7 @@ import time
 
 import numpy as np
 
+from ._call import launched, ptr as _p, stream as _stream
 from .utils._preprocess_utils import RawCounts, _to_csr, load_counts, timepoint_order
 
 TARGET_SUM = 1e4
@@ -68,21 +69,10 @@ def check_labels(labels, timepoint):
     return lab.astype(np.int32), tps, ks
 
 
-def _stream():
-    import ctypes
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
-    return t.data_ptr()
-
-
 def _check(rc, name):
     if rc == -7:
         raise ValueError(f"{name}: more than {MAX_DOMAINS} domains or more than {MAX_SPOTS} spots in a time point")
-    if rc != 0:
-        raise RuntimeError(f"{name} failed with code {rc}")
+    launched(rc, name)
 
 
 class MarkerKernels:

@@ -19,7 +19,8 @@ import torch
 import torch.nn as nn
 
 from .._lib import model_lib
-from ..ops import stamp_if, _SPLIT, _check, _p, _stream, elbo_reduce, kernel_matrix, rowdot, spd_inverse_logdet
+from .._call import launched as _check, ptr as _p, stream as _stream
+from ..ops import stamp_if, _SPLIT, elbo_reduce, kernel_matrix, rowdot, spd_inverse_logdet
 
 SWEEP_DIRECT_M = _SPLIT[0]      # up to here one sweep launch takes the matrices as they are (ops._spd_inverse_logdet_nograd)
 

@@ -29,6 +29,8 @@ import time
 
 import numpy as np
 
+from .utils._stage_utils import edge_pair
+
 MAX_CLUSTERS = 32
 MAX_NODES = 2147483647
 TABLE_COLUMNS = ("domain", "neighbor", "count", "expected", "sd", "zscore", "share", "p_enriched", "p_depleted", "padj")
@@ -79,23 +81,6 @@ def enrichment_stats(counts, perm_counts, sizes):
                 coherence=np.diagonal(share).copy())
 
 
-def _edge_pair(e, dev, g):
-    import torch
-    src, dst = e
-    src = src if isinstance(src, torch.Tensor) else torch.as_tensor(np.asarray(src))
-    dst = dst if isinstance(dst, torch.Tensor) else torch.as_tensor(np.asarray(dst))
-    for t in (src, dst):
-        if not t.is_cuda:
-            raise RuntimeError("spadot_amd counts neighbourhoods on the MI355X only (got a CPU tensor); there is no CPU path")
-        if t.dim() != 1 or t.dtype.is_floating_point or t.dtype == torch.bool or t.dtype.is_complex:
-            raise ValueError(f"the edges of graph {g} must be two 1-d integer tensors (got {tuple(t.shape)} {t.dtype})")
-    if src.shape != dst.shape or src.device != dst.device or (dev is not None and src.device != dev):
-        raise ValueError(f"the sources and targets of graph {g} must have one length and all graphs one device")
-    if src.shape[0] > MAX_NODES:
-        raise ValueError(f"graph {g} has {src.shape[0]} edges: the device takes at most {MAX_NODES} per graph")
-    return src, dst
-
-
 def _label_block(lab, dev, g):
     """An integer labeling block as a device tensor, with its smallest and largest label as 0-d device tensors."""
     import torch
@@ -114,7 +99,7 @@ def _run(edges, problems, lds_limit=None, out=None):
     `blocks` shared through problems[0]['blocks'], n, K, L, p0 (-1: explicit labelings), gid, seed.  One launch; returns the
     int32 [sum L, K_max, K_max] device tensor."""
     import torch
-    from .ops import NHOOD_DESC, nhood_counts as launch
+    from .stage_ops import NHOOD_DESC, nhood_counts as launch
     blocks = problems[0]["blocks"]
     dev = blocks[0].device
     with torch.cuda.device(dev):
@@ -153,7 +138,7 @@ def nhood_counts(edges, labelings, n_clusters=None, lds_limit=None, out=None):
         raise ValueError(f"n_clusters holds {len(n_clusters)} cluster counts for {len(edges)} graphs")
     pairs, dev = [], None
     for g, e in enumerate(edges):
-        pairs.append(_edge_pair(e, dev, g))
+        pairs.append(edge_pair(e, dev, g))
         dev = pairs[-1][0].device
     blocks, problems, ranges = [], [], []
     for g, lab in enumerate(labelings):
@@ -198,7 +183,7 @@ def nhood_enrichment(edges, labels, n_perms=1000, seed=0, n_clusters=None):
         raise ValueError(f"n_clusters holds {len(n_clusters)} cluster counts for {len(edges)} graphs")
     pairs, dev = [], None
     for g, e in enumerate(edges):
-        pairs.append(_edge_pair(e, dev, g))
+        pairs.append(edge_pair(e, dev, g))
         dev = pairs[-1][0].device
     blocks, ranges = [], []
     for g, lab in enumerate(labels):

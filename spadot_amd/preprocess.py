@@ -32,6 +32,7 @@ import sys
 import numpy as np
 import torch
 
+from ._call import launched as _check, ptr as _p, stream as _stream
 from ._lib import model_lib
 from .sctransform import sctransform
 from .utils._preprocess_utils import (N_KERNELS, RawCounts, by_adjust, kernel_coordinates, load_counts, rank_genes,  # noqa: F401
@@ -48,20 +49,6 @@ N_NEIGHBORS = 100              # sc.pp.neighbors(n_neighbors=100)
 GENE_CLUSTERS = ("kmeans", "louvain")
 PVAL_NODES = 256               # trapezoid nodes of the two-term survival function
 CSV_SUFFIX = "_SVG_sparkx_clustered_louvain.csv"
-
-
-def _stream():
-    import ctypes
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
-    return t.data_ptr()
-
-
-def _check(rc, name):
-    if rc != 0:
-        raise RuntimeError(f"{name} failed with code {rc}")
 
 
 class DeviceCounts:

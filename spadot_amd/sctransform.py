@@ -21,11 +21,10 @@ Deviations from the reference:
     resolution loop stops with an error past resolution 100 and targets min(10, S) communities for S genes.
 Quirks kept: `fitted` is the Poisson mean before the last coefficient update; theta is not clamped at min_theta (the
 reference's chained assignment is a no-op); ScaleData subtracts the float32-rounded row mean in fp64."""
-import ctypes
-
 import numpy as np
 import torch
 
+from ._call import launched as _check, ptr as _p, stream as _stream
 from ._lib import model_lib
 from .utils._sctransform_utils import regularize, sample_step1
 
@@ -37,19 +36,6 @@ POIS_TOL, POIS_MAXIT = 1e-9, 100          # qpois_reg(..., 1e-9, 100, ...)
 THETA_LIMIT, THETA_EPS = 10, 0.0001220703  # theta_ml(limit=10, eps=...)
 BW_ADJUST = 3
 RV_TH = 1.3
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
-    return t.data_ptr()
-
-
-def _check(rc, name):
-    if rc != 0:
-        raise RuntimeError(f"{name} failed with code {rc}")
 
 
 class SCTResult:

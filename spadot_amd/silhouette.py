@@ -118,7 +118,7 @@ class SilhouetteBatch:
 
     def launch(self):
         import torch
-        from .ops import silhouette_launch
+        from .stage_ops import silhouette_launch
         with torch.cuda.device(self.device):
             self.out = silhouette_launch(self.X, self.prob, self.order, self.coff, max(self.sizes), min(self.Ks),
                                          max(self.Ks), out=self.out)

@@ -1,0 +1,536 @@
+"""The launches of the analysis stages (silhouette, gmm, neighbors, cooccurrence, autocorr, ligrec) in libspadot_model.so
+(include/spadot_model.h).  A *_check refuses, before any launch, what the library would refuse or cannot see (ranges that only a
+reduction on the device knows: one host round trip); a *_launch hands over what the check returned.  CPU tensors raise."""
+import ctypes
+
+import numpy as np
+import torch
+
+from ._call import launched, need_cuda, ptr as _p, stream as _stream
+from ._lib import model_lib
+
+
+def _host(a):
+    return ctypes.c_void_p(a.ctypes.data)
+
+
+def _host_desc(desc, width, unit):
+    """The caller's descriptor as a fresh int64 [rows >= 1, width] host array in C order."""
+    desc = np.array(desc, dtype=np.int64, order="C", copy=True)
+    if desc.ndim != 2 or desc.shape[1] != width or desc.shape[0] < 1:
+        raise ValueError(f"a descriptor holds {width} numbers per {unit} (got an array of shape {desc.shape})")
+    return desc
+
+
+def _typed(*specs, any_dim=()):
+    for t, dt, what in specs:
+        if t.dtype != dt or not t.is_contiguous() or (t.dim() != 1 and what not in any_dim):
+            raise ValueError(f"{what} must be a contiguous 1-d {dt} tensor (got {tuple(t.shape)} {t.dtype})")
+
+
+def _edge_ends(src, dst, eoff, E, zero):
+    """[smallest, largest] edge end of the E edges from eoff on, as 0-d int64 device tensors (zeros without edges)."""
+    if E <= 0:
+        return [zero, zero]
+    lo_s, hi_s = torch.aminmax(src[eoff:eoff + E])
+    lo_d, hi_d = torch.aminmax(dst[eoff:eoff + E])
+    return [torch.minimum(lo_s, lo_d).long(), torch.maximum(hi_s, hi_d).long()]
+
+
+def _refuse_edge_ends(unit, i, lo, hi, n, E):
+    if E > 0 and (lo < 0 or hi >= n):
+        raise ValueError(f"{unit} {i} has edge ends {int(lo)} .. {int(hi)}: they must lie in 0 .. {n - 1}")
+
+
+def _csc_stats(colptr, ridx, zero):
+    """[smallest row index, largest, colptr[0], colptr[-1], colptr descends somewhere] as 0-d int64 device tensors."""
+    lo, hi = torch.aminmax(ridx) if ridx.numel() > 0 else (zero, zero)
+    return [lo.long(), hi.long(), colptr[0], colptr[-1], (colptr[1:] < colptr[:-1]).any().long()]
+
+
+def _refuse_rows(ridx_lo, ridx_hi, nnz, rows):
+    if nnz > 0 and (ridx_lo < 0 or ridx_hi >= rows):
+        raise ValueError(f"ridx holds the row indices {ridx_lo} .. {ridx_hi}: they must lie in 0 .. {rows - 1}")
+
+
+def _refuse_colptr(c0, c1, unordered, nnz):
+    if c0 != 0 or c1 != nnz or unordered:
+        raise ValueError(f"colptr must ascend from 0 to the {nnz} stored entries (it runs from {c0} to {c1})")
+
+
+def _csc_sizes(colptr, ridx, values, limit):
+    G, nnz = int(colptr.numel()) - 1, int(ridx.numel())
+    if G < 1 or values.numel() != nnz or nnz > limit:
+        raise ValueError(f"colptr holds {G} genes, ridx {nnz} and values {int(values.numel())} stored entries: at least one gene, "
+                         f"one value per entry and at most {limit} entries")
+    return G, nnz
+
+
+def _labelings(name, observed, first, P):
+    """(observed as 0 / 1, first, P) of a call over the observed labeling and / or the permutations first .. first + P - 1."""
+    observed, first, P = int(bool(observed)), int(first), int(P)
+    if P < 0 or first < 0 or observed + P < 1:
+        raise ValueError(f"{name} takes P >= 0 permutations from first >= 0 on, and at least one labeling (got P = {P}, "
+                         f"first = {first}, observed = {bool(observed)})")
+    if first + P > 2 ** 32:
+        raise ValueError(f"permutation indices {first} .. {first + P - 1}: the indices must stay below 2^32")
+    return observed, first, P
+
+
+def _lds_limit(lds_limit, most):
+    lds_limit = most if lds_limit is None else min(int(lds_limit), most)
+    if lds_limit < 0:
+        raise ValueError(f"lds_limit is a number of bytes, 0 to {most} (got {lds_limit})")
+    return lds_limit
+
+
+def _signed64(seed):
+    seed = int(seed) & (2 ** 64 - 1)
+    return seed - 2 ** 64 if seed >= 2 ** 63 else seed
+
+
+def silhouette_launch(X, prob, order, coff, n_max, k_min, k_max, out=None):
+    """Silhouette coefficients of P (data set, labeling) problems in ONE launch (include/spadot_model.h: spadot_silhouette).
+    X [rows, d] fp64, the sets one after the other; prob [P, 4] int64 (first row of the set, offset of the problem, n, K);
+    order int32 [sum n]: per problem its rows sorted by (label, row); coff int32 [P, 33] cluster offsets.  Returns (a, b,
+    nearest, s) of length sum n in the caller's row order (out: tensors to write into).  ValueError outside 1 <= d <= 32,
+    2 <= K <= 32, P <= 65535, n <= 2147483391, before any launch."""
+    need_cuda(X, prob, order, coff)
+    if X.dtype != torch.float64 or not X.is_contiguous():
+        raise RuntimeError("silhouette_launch takes a contiguous fp64 matrix")
+    total, P = int(order.shape[0]), int(prob.shape[0])
+    a, b, nearest, s = out if out is not None else (
+        torch.empty(total, dtype=torch.float64, device=X.device), torch.empty(total, dtype=torch.float64, device=X.device),
+        torch.empty(total, dtype=torch.int32, device=X.device), torch.empty(total, dtype=torch.float64, device=X.device))
+    rc = model_lib().spadot_silhouette(_p(X), int(X.shape[1]), P, _p(prob), _p(order), _p(coff), int(n_max), int(k_min),
+                                       int(k_max), _p(a), _p(b), _p(nearest), _p(s), _stream())
+    launched(rc, "spadot_silhouette", "1 <= d <= 32, 2 <= K <= 32, at most 65535 problems of at most 2147483391 points",
+             f": d = {int(X.shape[1])}, K = {int(k_min)} .. {int(k_max)}, {P} problems, n <= {int(n_max)}")
+    return a, b, nearest, s
+
+
+GMM_LIMITS = ("1 <= d <= 32, 1 <= K <= 32, at most 65535 problems of at most 2147483391 points, and 8 (max(K S, (K + 256) DP) + "
+              "256 (K | 1)) + 2048 <= 163840 bytes of LDS with DP = 4 ceil(d / 4), S = DP + DP (DP + 1) / 2 + 2 (K = 32 up to "
+              "d = 24, K <= 29 up to d = 28, K <= 24 up to d = 32)")
+
+
+def gmm_em_steps(X, prob, n_max, par, w, cov, part, done, n_iter, lb, reg_covar, tol, steps, resp_init=None, mom=None):
+    """Gaussian-mixture EM for P problems (include/spadot_model.h: spadot_gmm_em_step): if resp_init is given, first the M-step
+    from those responsibilities; then `steps` iterations (E-step, M-step, stop rule), frozen problems left alone.  X [rows, d]
+    centred fp64; prob [P, 4] int64; par [P, K_max, S], w [P, K_max], cov [P, K_max, d, d], mom [P, K_max, M] or None, part (work
+    space), done / n_iter int32 [P], lb fp64 [P]: updated in place.  ValueError outside the limits, before any launch."""
+    need_cuda(X, prob, par, w, cov, part, done, n_iter, lb, resp_init, mom)
+    if X.dtype != torch.float64 or not X.is_contiguous():
+        raise RuntimeError("gmm_em_steps takes a contiguous fp64 matrix")
+    P, K_max, d = int(prob.shape[0]), int(par.shape[1]), int(X.shape[1])
+    rc = model_lib().spadot_gmm_em_step(_p(X), d, P, _p(prob), K_max, int(n_max), _p(par), _p(w), _p(cov), _p(mom),
+                                        _p(resp_init), float(reg_covar), float(tol), int(steps), _p(part), _p(done), _p(n_iter),
+                                        _p(lb), _stream())
+    launched(rc, "spadot_gmm_em_step", GMM_LIMITS, f": d = {d}, K = {K_max}, {P} problems, n <= {int(n_max)}")
+
+
+def gmm_estep(X, prob, n_max, par, norm, labels=None, resp=None, lp=None):
+    """One E-step of P problems with the parameters in par (spadot_gmm_estep): norm [sum n] fp64 and, where given, labels [sum n]
+    int32, resp and lp [sum n, K_max] fp64 are written.  ValueError outside the limits, before any launch."""
+    need_cuda(X, prob, par, norm, labels, resp, lp)
+    if X.dtype != torch.float64 or not X.is_contiguous():
+        raise RuntimeError("gmm_estep takes a contiguous fp64 matrix")
+    P, K_max, d = int(prob.shape[0]), int(par.shape[1]), int(X.shape[1])
+    rc = model_lib().spadot_gmm_estep(_p(X), d, P, _p(prob), K_max, int(n_max), _p(par), _p(norm), _p(labels), _p(resp), _p(lp),
+                                      _stream())
+    launched(rc, "spadot_gmm_estep", GMM_LIMITS, f": d = {d}, K = {K_max}, {P} problems, n <= {int(n_max)}")
+
+
+NHOOD_MAX_K = 32
+NHOOD_MAX = 2147483647             # nodes and edges of a graph (int32), and (graph, labeling) pairs of a call (gridDim.x)
+NHOOD_LDS_BYTES = 163840
+NHOOD_DESC = 12
+NHOOD_LIMITS = ("1 <= K <= 32, 1 <= n <= 2147483647 nodes and at most 2147483647 edges per graph, every edge end in 0 .. n-1, every "
+                "label below K, at most 2147483647 labelings per call, permutation indices below 2^32")
+
+
+def nhood_check(src, dst, labels, desc, K_max):
+    """The refusals of nhood_counts, before any launch: the limits from the descriptor, then the range of the edge ends and the
+    largest label of every graph by reductions on the device (one host round trip).  Returns the descriptor with columns 10 and
+    11 filled in; ValueError otherwise."""
+    need_cuda(src, dst, labels)
+    desc = _host_desc(desc, NHOOD_DESC, "graph")
+    K_max = int(K_max)
+    if not 1 <= K_max <= NHOOD_MAX_K:
+        raise ValueError(f"spadot_nhood_counts takes 1 to {NHOOD_MAX_K} label values (got K_max = {K_max})")
+    items = 0
+    for g, (eoff, n, E, K, loff, L, p0, gid, item0, _seed, _lo, _hi) in enumerate(desc.tolist()):
+        if not 1 <= K <= K_max:
+            raise ValueError(f"graph {g} has {K} label values: spadot_nhood_counts takes 1 to {K_max} here, at most {NHOOD_MAX_K}")
+        if not 1 <= n <= NHOOD_MAX:
+            raise ValueError(f"graph {g} has {n} nodes: spadot_nhood_counts takes 1 to {NHOOD_MAX} (int32 node numbers)")
+        if not 0 <= E <= NHOOD_MAX:
+            raise ValueError(f"graph {g} has {E} edges: spadot_nhood_counts takes at most {NHOOD_MAX} per graph")
+        if L < 1 or item0 != items or eoff < 0 or loff < 0 or p0 < -1 or gid < 0:
+            raise ValueError(f"graph {g}: inconsistent descriptor {desc[g].tolist()}")
+        if p0 >= 0 and (p0 + L > 2 ** 32 or gid > NHOOD_MAX):
+            raise ValueError(f"graph {g}: permutation indices {p0} .. {p0 + L - 1} of graph id {gid}: the indices must stay below "
+                             f"2^32 and the graph id below 2^31")
+        items += L
+        if items > NHOOD_MAX:
+            raise ValueError(f"the call holds more than {NHOOD_MAX} labelings (the grid of one launch)")
+    _typed((src, torch.int32, "src"), (dst, torch.int32, "dst"), (labels, torch.uint8, "labels"))
+    zero = torch.zeros((), dtype=torch.int64, device=labels.device)
+    stats = []
+    for g, (eoff, n, E, K, loff, L, p0, *_rest) in enumerate(desc.tolist()):
+        nlab = n if p0 >= 0 else L * n
+        if eoff + E > src.numel() or eoff + E > dst.numel() or loff + nlab > labels.numel():
+            raise ValueError(f"graph {g}: its edges or labels reach past the end of the tensors")
+        stats += _edge_ends(src, dst, eoff, E, zero) + [labels[loff:loff + nlab].max().long()]
+    stats = torch.stack(stats).cpu().numpy().reshape(-1, 3)            # the one host round trip ahead of the launch
+    desc[:, 10], desc[:, 11] = stats[:, 0], stats[:, 1]
+    for g in range(desc.shape[0]):
+        n, E, K = (int(v) for v in desc[g, 1:4])
+        _refuse_edge_ends("graph", g, stats[g, 0], stats[g, 1], n, E)
+        if stats[g, 2] >= K:
+            raise ValueError(f"graph {g} holds the label {int(stats[g, 2])}: labels must lie in 0 .. {K - 1}")
+    return desc
+
+
+def nhood_launch(src, dst, labels, desc, K_max, lds_limit=None, out=None, desc_dev=None):
+    """The launch of nhood_counts for a descriptor that nhood_check has returned (the library checks it again, on the host)."""
+    need_cuda(src, dst, labels, out, desc_dev)
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    K_max, items = int(K_max), int(desc[:, 5].sum())
+    lds_limit = _lds_limit(lds_limit, NHOOD_LDS_BYTES)
+    if out is None:
+        out = torch.empty((items, K_max, K_max), dtype=torch.int32, device=labels.device)
+    elif out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != items * K_max * K_max:
+        raise ValueError(f"out must be a contiguous int32 tensor of {items} x {K_max} x {K_max} values")
+    if desc_dev is None:
+        desc_dev = torch.as_tensor(desc, device=labels.device)
+    launched(model_lib().spadot_nhood_counts(_p(src), _p(dst), _p(labels), _host(desc), _p(desc_dev), int(desc.shape[0]), K_max,
+                                             lds_limit, _p(out), _stream()), "spadot_nhood_counts", NHOOD_LIMITS)
+    return out
+
+
+def nhood_counts(src, dst, labels, desc, K_max, lds_limit=None, out=None):
+    """Label-pair edge counts of many (graph, labeling) problems in ONE launch (include/spadot_model.h: spadot_nhood_counts).
+    src, dst int32 and labels uint8 device tensors, the graphs back to back; desc: int64 [G, 12] on the host as the header lays
+    it out (columns 10 and 11, the range of the edge ends, are filled in here).  lds_limit: the LDS bytes a workgroup may use
+    (default and at most 163840); a graph whose labels do not fit reads them from global memory.  Returns int32
+    [sum L, K_max, K_max] (out: the tensor to write into).  ValueError, before any launch, outside the limits."""
+    return nhood_launch(src, dst, labels, nhood_check(src, dst, labels, desc, K_max), K_max, lds_limit, out)
+
+
+COOCCUR_MAX_K = 32
+COOCCUR_MAX_B = 64
+COOCCUR_GRANULE = 16               # the thresholds of a problem are padded to a multiple of this with -1.0
+COOCCUR_MAX_N = 2147483391         # spots of a problem: int32 positions of a 256-wide tile (as spadot_silhouette)
+COOCCUR_MAX_P = 65535              # problems of a call (gridDim.y)
+COOCCUR_DESC = 40
+COOCCUR_LIMITS = ("1 <= K <= 32 label values, 1 <= B <= 64 thresholds that are finite, >= 0 and strictly increasing, "
+                  "1 <= n <= 2147483391 spots per problem, at most 65535 problems per call")
+
+
+def cooccur_padded(B_max):
+    """The threshold columns of a call whose largest problem has B_max thresholds."""
+    return (int(B_max) + COOCCUR_GRANULE - 1) // COOCCUR_GRANULE * COOCCUR_GRANULE
+
+
+def cooccur_check(xy, desc, r2, K_max, B_max):
+    """The refusals of cooccur_counts that the descriptor and the thresholds decide, before any launch.  Returns (desc int64
+    [P, 40], r2 fp64 [P, BP] padded with -1.0); ValueError otherwise.  r2: [P] sequences of squared thresholds, or the padded
+    array itself."""
+    need_cuda(xy)
+    desc = _host_desc(desc, COOCCUR_DESC, "problem")
+    K_max, B_max, P = int(K_max), int(B_max), desc.shape[0]
+    if not 1 <= K_max <= COOCCUR_MAX_K:
+        raise ValueError(f"spadot_cooccur_counts takes 1 to {COOCCUR_MAX_K} label values (got K_max = {K_max})")
+    if not 1 <= B_max <= COOCCUR_MAX_B:
+        raise ValueError(f"spadot_cooccur_counts takes 1 to {COOCCUR_MAX_B} thresholds (got B_max = {B_max})")
+    if P > COOCCUR_MAX_P:
+        raise ValueError(f"the call holds {P} problems: spadot_cooccur_counts takes at most {COOCCUR_MAX_P} (the grid of one "
+                         f"launch)")
+    if len(r2) != P:
+        raise ValueError(f"the call holds {P} problems and {len(r2)} sets of thresholds")
+    BP = cooccur_padded(B_max)
+    pad = np.full((P, BP), -1.0, dtype=np.float64)
+    first = 0
+    for p, row in enumerate(desc.tolist()):
+        off, n, K, B = row[:4]
+        if not 1 <= K <= K_max:
+            raise ValueError(f"problem {p} has {K} label values: spadot_cooccur_counts takes 1 to {K_max} here, at most "
+                             f"{COOCCUR_MAX_K}")
+        if not 1 <= B <= B_max:
+            raise ValueError(f"problem {p} has {B} thresholds: spadot_cooccur_counts takes 1 to {B_max} here, at most "
+                             f"{COOCCUR_MAX_B}")
+        if not 1 <= n <= COOCCUR_MAX_N:
+            raise ValueError(f"problem {p} has {n} spots: spadot_cooccur_counts takes 1 to {COOCCUR_MAX_N} (int32 positions)")
+        coff = row[4:5 + K]
+        if off != first or coff[0] != 0 or coff[-1] != n or any(hi < lo for lo, hi in zip(coff, coff[1:])):
+            raise ValueError(f"problem {p}: inconsistent descriptor {row[:5 + K]}")
+        first += n
+        t = np.asarray(r2[p], dtype=np.float64).reshape(-1)
+        if t.shape[0] == BP and np.all(t[B:] == -1.0):
+            t = t[:B]
+        if t.shape[0] != B:
+            raise ValueError(f"problem {p} has {t.shape[0]} thresholds and its descriptor says {B}")
+        if not np.all(np.isfinite(t)) or np.any(t < 0) or np.any(np.diff(t) <= 0):
+            raise ValueError(f"the squared thresholds of problem {p} must be finite, >= 0 and strictly increasing")
+        pad[p, :B] = t
+    if xy.dtype != torch.float64 or xy.dim() != 2 or xy.shape[1] != 2 or not xy.is_contiguous() or xy.shape[0] != first:
+        raise ValueError(f"xy must be a contiguous fp64 [{first}, 2] tensor (got {tuple(xy.shape)} {xy.dtype})")
+    return desc, pad
+
+
+def cooccur_launch(xy, desc, r2, K_max, B_max, out=None, desc_dev=None, r2_dev=None):
+    """The launch of cooccur_counts for what cooccur_check has returned (the library checks both again, on the host)."""
+    need_cuda(xy, out, desc_dev, r2_dev)
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    r2 = np.ascontiguousarray(r2, dtype=np.float64)
+    K_max, B_max, P = int(K_max), int(B_max), int(desc.shape[0])
+    if out is None:
+        out = torch.empty((P, K_max, K_max, B_max), dtype=torch.int64, device=xy.device)
+    elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != P * K_max * K_max * B_max:
+        raise ValueError(f"out must be a contiguous int64 tensor of {P} x {K_max} x {K_max} x {B_max} values")
+    if desc_dev is None:
+        desc_dev = torch.as_tensor(desc, device=xy.device)
+    if r2_dev is None:
+        r2_dev = torch.as_tensor(r2, device=xy.device)
+    launched(model_lib().spadot_cooccur_counts(_p(xy), _host(desc), _p(desc_dev), _host(r2), _p(r2_dev), P, K_max, B_max, _p(out),
+                                               _stream()), "spadot_cooccur_counts", COOCCUR_LIMITS)
+    return out
+
+
+def cooccur_counts(xy, desc, r2, K_max, B_max, out=None):
+    """Label-pair counts by distance of many problems in ONE counting launch (include/spadot_model.h: spadot_cooccur_counts).
+    xy: fp64 [sum n, 2] device tensor, per problem its spots ordered by (label, index), the problems back to back; desc: int64
+    [P, 40] on the host as the header lays it out; r2[p]: the squared thresholds of problem p.  Returns int64
+    [P, K_max, K_max, B_max] (out: the tensor to write into).  ValueError, before any launch, outside the limits."""
+    desc, pad = cooccur_check(xy, desc, r2, K_max, B_max)
+    return cooccur_launch(xy, desc, pad, K_max, B_max, out)
+
+
+AUTOCORR_DESC = 7
+AUTOCORR_MAX = 2147483647          # spots, edges and stored entries (int32), graph ids, and workgroups of a call (gridDim.x)
+AUTOCORR_LDS_BYTES = 163840
+AUTOCORR_LDS_FIXED = 2048          # LDS beside the image: the reduction and the segment bounds
+AUTOCORR_THREADS = 1024            # the library's defaults (Time)
+AUTOCORR_GS = 2
+AUTOCORR_LIMITS = ("1 <= n <= 2147483647 spots and at most 2147483647 edges per time point, at most 2147483647 stored entries, every "
+                   "edge end in 0 .. n-1, every row index inside the time points, permutation indices below 2^32, at most "
+                   "2147483647 workgroups per call, threads in (256, 512, 1024), gs in (2, 4)")
+
+
+def autocorr_check(src, dst, colptr, ridx, values, centre, desc, g0, ng, observed, first, P):
+    """The refusals of autocorr_sums, before any launch: the limits from the descriptor and the ranges, then the range of the
+    edge ends of every time point, the range of the row indices and the order of colptr by reductions on the device (one host
+    round trip).  Returns (the descriptor with columns 5 and 6 filled in, the smallest row index, the largest); ValueError
+    otherwise."""
+    need_cuda(src, dst, colptr, ridx, values, centre)
+    desc = _host_desc(desc, AUTOCORR_DESC, "time point")
+    T, g0, ng = int(desc.shape[0]), int(g0), int(ng)
+    _typed((src, torch.int32, "src"), (dst, torch.int32, "dst"), (ridx, torch.int32, "ridx"), (colptr, torch.int64, "colptr"),
+           (values, torch.float32, "values"), (centre, torch.float64, "centre"), any_dim=("centre",))
+    G, nnz = _csc_sizes(colptr, ridx, values, AUTOCORR_MAX)
+    if tuple(centre.shape) != (T, G):
+        raise ValueError(f"centre must be [T, G] = [{T}, {G}] (got {tuple(centre.shape)})")
+    if g0 < 0 or ng < 1 or g0 + ng > G:
+        raise ValueError(f"the genes {g0} .. {g0 + ng - 1} are not a range of the {G} genes")
+    observed, first, P = _labelings("autocorr_sums", observed, first, P)
+    rows = 0
+    for t, (eoff, n, E, row0, gid, _lo, _hi) in enumerate(desc.tolist()):
+        if not 1 <= n <= AUTOCORR_MAX:
+            raise ValueError(f"time point {t} has {n} spots: spadot_autocorr_sums takes 1 to {AUTOCORR_MAX} (int32 spot numbers)")
+        if not 0 <= E <= AUTOCORR_MAX:
+            raise ValueError(f"time point {t} has {E} edges: spadot_autocorr_sums takes at most {AUTOCORR_MAX} per time point")
+        if eoff < 0 or not 0 <= row0 <= AUTOCORR_MAX or not 0 <= gid <= AUTOCORR_MAX:
+            raise ValueError(f"time point {t}: inconsistent descriptor {desc[t].tolist()}")
+        if eoff + E > src.numel() or eoff + E > dst.numel():
+            raise ValueError(f"time point {t}: its edges reach past the end of the tensors")
+        rows = max(rows, row0 + n)
+    if T * (observed + P) * -(-ng // 2) > AUTOCORR_MAX:
+        raise ValueError(f"the call holds more than {AUTOCORR_MAX} workgroups (the grid of one launch)")
+    zero = torch.zeros((), dtype=torch.int64, device=colptr.device)
+    stats = [s for eoff, _n, E, *_rest in desc.tolist() for s in _edge_ends(src, dst, eoff, E, zero)]
+    stats = torch.stack(stats + _csc_stats(colptr, ridx, zero)).cpu().numpy()   # the one host round trip ahead of the launch
+    ends = stats[:2 * T].reshape(T, 2)
+    desc[:, 5], desc[:, 6] = ends[:, 0], ends[:, 1]
+    for t in range(T):
+        _refuse_edge_ends("time point", t, ends[t, 0], ends[t, 1], int(desc[t, 1]), int(desc[t, 2]))
+    ridx_lo, ridx_hi, c0, c1, unordered = (int(v) for v in stats[2 * T:])
+    _refuse_rows(ridx_lo, ridx_hi, nnz, rows)
+    _refuse_colptr(c0, c1, unordered, nnz)
+    return desc, ridx_lo, ridx_hi
+
+
+def autocorr_scratch_floats(desc, ng, L, lds_limit=None, gs=None):
+    """The floats of the scratch buffer of a call (0: every image fits in LDS), as the library computes it."""
+    gs = AUTOCORR_GS if not gs else int(gs)
+    lds_limit = AUTOCORR_LDS_BYTES if lds_limit is None else min(int(lds_limit), AUTOCORR_LDS_BYTES)
+    slab = max([(gs * int(n) + 3) & ~3 for n in desc[:, 1] if AUTOCORR_LDS_FIXED + 4 * gs * int(n) > lds_limit] or [0])
+    return slab * int(desc.shape[0]) * int(L) * -(-int(ng) // gs)
+
+
+def autocorr_launch(src, dst, colptr, ridx, values, centre, checked, g0, ng, observed, first, P, seed=0, lds_limit=None, out=None,
+                    scratch=None, threads=None, gs=None, desc_dev=None):
+    """The launch of autocorr_sums for what autocorr_check has returned (the library checks the descriptor again, on the host)."""
+    desc, ridx_lo, ridx_hi = checked
+    need_cuda(src, dst, colptr, ridx, values, centre, scratch, desc_dev, *(out or ()))
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    T, G, L = int(desc.shape[0]), int(colptr.numel()) - 1, int(bool(observed)) + int(P)
+    lds_limit = _lds_limit(lds_limit, AUTOCORR_LDS_BYTES)
+    threads, gs = int(threads or 0), int(gs or 0)
+    if threads not in (0, 256, 512, 1024) or gs not in (0, 2, 4):         # the library's refusal, ahead of the call
+        launched(-7, "spadot_autocorr_sums", AUTOCORR_LIMITS)
+    dev = colptr.device
+    if out is None:
+        out = tuple(torch.empty((T, int(ng), L), dtype=torch.float64, device=dev) for _ in range(2))
+    elif len(out) != 2 or any(o.dtype != torch.float64 or not o.is_contiguous() or o.numel() != T * int(ng) * L for o in out):
+        raise ValueError(f"out must be two contiguous float64 tensors of {T} x {int(ng)} x {L} values")
+    need = autocorr_scratch_floats(desc, ng, L, lds_limit, gs)
+    if need and scratch is None:
+        scratch = torch.empty(need, dtype=torch.float32, device=dev)
+    elif need and (scratch.dtype != torch.float32 or not scratch.is_contiguous() or scratch.numel() < need):
+        raise ValueError(f"scratch must be a contiguous float32 tensor of at least {need} values")
+    if desc_dev is None:
+        desc_dev = torch.as_tensor(desc, device=dev)
+    rc = model_lib().spadot_autocorr_sums(_p(src), _p(dst), _p(colptr), _p(ridx), _p(values), int(ridx.numel()), ridx_lo, ridx_hi,
+                                          _p(centre), _host(desc), _p(desc_dev), T, G, int(g0), int(ng), int(bool(observed)),
+                                          int(first), int(P), _signed64(seed), lds_limit, _p(scratch) if need else None,
+                                          int(scratch.numel()) if need else 0, threads, gs, _p(out[0]), _p(out[1]), _stream())
+    launched(rc, "spadot_autocorr_sums", AUTOCORR_LIMITS)
+    return out
+
+
+def autocorr_sums(src, dst, colptr, ridx, values, centre, desc, g0, ng, observed, first, P, seed=0, lds_limit=None, out=None,
+                  scratch=None, threads=None, gs=None):
+    """The edge sums N and D behind Moran's I and Geary's C of every (time point, gene, labeling) in ONE launch
+    (include/spadot_model.h: spadot_autocorr_sums).  src, dst int32 edge ends of the time points back to back; colptr int64,
+    ridx int32 and values fp32: the CSC arrays of a DeviceCounts; centre fp64 [T, G]; desc: int64 [T, 7] on the host as the
+    header lays it out (columns 5 and 6, the range of the edge ends, are filled in here).  Labelings: the identity (observed)
+    and the permutations first .. first + P - 1 under seed.  lds_limit: the LDS bytes a workgroup may use (default and at most
+    163840); a time point whose image does not fit keeps it in `scratch` (allocated here when not given).  Returns (N, D), fp64
+    device tensors [T, ng, observed + P] (out: the pair to write into).  ValueError, before any launch, outside the limits;
+    RuntimeError for a CPU tensor."""
+    checked = autocorr_check(src, dst, colptr, ridx, values, centre, desc, g0, ng, observed, first, P)
+    return autocorr_launch(src, dst, colptr, ridx, values, centre, checked, g0, ng, observed, first, P, seed, lds_limit, out,
+                           scratch, threads, gs)
+
+
+LIGREC_DESC = 3
+LIGREC_MAX_K = 32
+LIGREC_MAX = 2147483647            # spots and stored entries (int32), graph ids, and workgroups of a call (gridDim.x)
+LIGREC_LDS_BYTES = 163840
+LIGREC_THREADS = 512               # the library's defaults (Time)
+LIGREC_GC = 128
+LIGREC_LIMITS = ("1 <= K <= 32 label values, every label below K, 1 <= n <= 2147483647 spots per time point, at most 2147483647 "
+                 "stored entries, every row index inside the time points, every selected gene inside the genes, permutation "
+                 "indices below 2^32, at most 2147483647 workgroups per call, threads in (256, 512), gene_chunk >= 1")
+
+
+def ligrec_lds_bytes(n, K, threads=None):
+    """The LDS bytes a workgroup needs to keep the labels of a time point of n spots beside its accumulators."""
+    return int(threads or LIGREC_THREADS) // 64 * int(K) * 512 + ((int(n) + 15) & ~15)
+
+
+def ligrec_check(colptr, ridx, values, labels, genes, desc, K, observed, first, P, gene_chunk=None):
+    """The refusals of ligrec_sums, before any launch: the limits from the descriptor and the ranges, then the range of the row
+    indices, of the labels and of the selected genes and the order of colptr by reductions on the device (one host round trip).
+    Returns (the descriptor, the smallest row index, the largest, the largest label, the smallest selected gene, the largest);
+    ValueError otherwise."""
+    need_cuda(colptr, ridx, values, labels, genes)
+    desc = _host_desc(desc, LIGREC_DESC, "time point")
+    T, K = int(desc.shape[0]), int(K)
+    gc = LIGREC_GC if not gene_chunk else int(gene_chunk)
+    _typed((ridx, torch.int32, "ridx"), (colptr, torch.int64, "colptr"), (values, torch.float32, "values"),
+           (labels, torch.uint8, "labels"), (genes, torch.int32, "genes"))
+    if not 1 <= K <= LIGREC_MAX_K:
+        raise ValueError(f"spadot_ligrec_sums takes 1 to {LIGREC_MAX_K} label values (got K = {K})")
+    (G, nnz), ng = _csc_sizes(colptr, ridx, values, LIGREC_MAX), int(genes.numel())
+    if ng < 1 or gc < 1:
+        raise ValueError(f"spadot_ligrec_sums takes at least one selected gene and gene_chunk >= 1 (got {ng} genes, gene_chunk = "
+                         f"{gc})")
+    observed, first, P = _labelings("ligrec_sums", observed, first, P)
+    rows = 0
+    for t, (n, row0, gid) in enumerate(desc.tolist()):
+        if not 1 <= n <= LIGREC_MAX:
+            raise ValueError(f"time point {t} has {n} spots: spadot_ligrec_sums takes 1 to {LIGREC_MAX} (int32 spot numbers)")
+        if not 0 <= row0 <= LIGREC_MAX or not 0 <= gid <= LIGREC_MAX:
+            raise ValueError(f"time point {t}: inconsistent descriptor {desc[t].tolist()}")
+        rows = max(rows, row0 + n)
+    if labels.numel() < rows:
+        raise ValueError(f"labels holds {int(labels.numel())} bytes: one per row of the time points, {rows}")
+    if T * (observed + P) * -(-ng // gc) > LIGREC_MAX:
+        raise ValueError(f"the call holds more than {LIGREC_MAX} workgroups (the grid of one launch)")
+    zero = torch.zeros((), dtype=torch.int64, device=colptr.device)
+    stats = _csc_stats(colptr, ridx, zero) + [s.long() for s in (labels[:rows].max(), *torch.aminmax(genes))]
+    ridx_lo, ridx_hi, c0, c1, unordered, label_hi, gene_lo, gene_hi = (
+        int(v) for v in torch.stack(stats).cpu().numpy())                                        # the one host round trip
+    _refuse_rows(ridx_lo, ridx_hi, nnz, rows)
+    if label_hi >= K:
+        raise ValueError(f"labels holds the label {label_hi}: labels must lie in 0 .. {K - 1}")
+    if gene_lo < 0 or gene_hi >= G:
+        raise ValueError(f"the selected genes {gene_lo} .. {gene_hi} must lie in 0 .. {G - 1}")
+    _refuse_colptr(c0, c1, unordered, nnz)
+    return desc, ridx_lo, ridx_hi, label_hi, gene_lo, gene_hi
+
+
+def ligrec_launch(colptr, ridx, values, labels, genes, checked, K, observed, first, P, seed=0, lds_limit=None, out=None,
+                  threads=None, gene_chunk=None, desc_dev=None):
+    """The launch of ligrec_sums for what ligrec_check has returned (the library checks the descriptor again, on the host)."""
+    desc, ridx_lo, ridx_hi, label_hi, gene_lo, gene_hi = checked
+    need_cuda(colptr, ridx, values, labels, genes, desc_dev, *(out or ()))
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    T, G, K, ng = int(desc.shape[0]), int(colptr.numel()) - 1, int(K), int(genes.numel())
+    observed, L = int(bool(observed)), int(bool(observed)) + int(P)
+    lds_limit = _lds_limit(lds_limit, LIGREC_LDS_BYTES)
+    threads, gc = int(threads or 0), int(gene_chunk or 0)
+    if threads not in (0, 256, 512) or gc < 0:                            # the library's refusal, ahead of the call
+        launched(-7, "spadot_ligrec_sums", LIGREC_LIMITS)
+    dev = colptr.device
+    if out is None:
+        out = (torch.empty((T, L, ng, K), dtype=torch.float64, device=dev),
+               torch.empty((T, ng, K), dtype=torch.int32, device=dev) if observed else None)
+    elif (len(out) != 2 or out[0].dtype != torch.float64 or not out[0].is_contiguous() or out[0].numel() != T * L * ng * K
+          or (observed and (out[1] is None or out[1].dtype != torch.int32 or not out[1].is_contiguous()
+                            or out[1].numel() != T * ng * K))):
+        raise ValueError(f"out must be a contiguous float64 tensor of {T} x {L} x {ng} x {K} values and, with the observed "
+                         f"labeling, a contiguous int32 tensor of {T} x {ng} x {K}")
+    if desc_dev is None:
+        desc_dev = torch.as_tensor(desc, device=dev)
+    rc = model_lib().spadot_ligrec_sums(_p(colptr), _p(ridx), _p(values), int(ridx.numel()), ridx_lo, ridx_hi, _p(labels), label_hi,
+                                        _host(desc), _p(desc_dev), T, G, K, _p(genes), ng, gene_lo, gene_hi, observed, int(first),
+                                        int(P), _signed64(seed), lds_limit, threads, gc, _p(out[0]),
+                                        _p(out[1]) if observed else None, _stream())
+    launched(rc, "spadot_ligrec_sums", LIGREC_LIMITS)
+    return out
+
+
+def ligrec_sums(colptr, ridx, values, labels, genes, desc, K, observed, first, P, seed=0, lds_limit=None, out=None, threads=None,
+                gene_chunk=None):
+    """The per-domain expression sums of the selected genes of every (time point, labeling) in ONE launch
+    (include/spadot_model.h: spadot_ligrec_sums).  colptr int64, ridx int32 and values fp32: the CSC arrays of a DeviceCounts;
+    labels uint8, one per row; genes int32: the selected genes; desc: int64 [T, 3] on the host as the header lays it out.
+    Labelings: the labels themselves (observed) and the permutations first .. first + P - 1 under seed.  lds_limit: the LDS
+    bytes a workgroup may use (default and at most 163840); a time point whose labels do not fit beside the accumulators
+    permutes per stored entry.  Returns (S fp64 [T, observed + P, genes, K], c int32 [T, genes, K] or None without the observed
+    labeling) on the device (out: the pair to write into).  ValueError, before any launch, outside the limits; RuntimeError for a
+    CPU tensor."""
+    checked = ligrec_check(colptr, ridx, values, labels, genes, desc, K, observed, first, P, gene_chunk)
+    return ligrec_launch(colptr, ridx, values, labels, genes, checked, K, observed, first, P, seed, lds_limit, out, threads,
+                         gene_chunk)
+
+
+def ligrec_count(S0, S, wk, pairs, pair_range, mask, skip, ge):
+    """Adds, for every masked cell, the labelings l >= skip of the run S [T, L, ns, K] whose statistic is at least that of S0
+    [T, ns, K] into ge int32 [T, M, K, K] (include/spadot_model.h: spadot_ligrec_count).  wk fp64 [T, K]; pairs int32 [M, 2]
+    positions in the selected genes, pair_range their (smallest, largest); mask uint8 [T, M, K, K]."""
+    need_cuda(S0, S, wk, pairs, mask, ge)
+    T, L, ns, K = (int(v) for v in S.shape)
+    M = int(pairs.shape[0])
+    for t, dt, shape, what in ((S0, torch.float64, (T, ns, K), "S0"), (S, torch.float64, (T, L, ns, K), "S"),
+                               (wk, torch.float64, (T, K), "wk"), (pairs, torch.int32, (M, 2), "pairs"),
+                               (mask, torch.uint8, (T, M, K, K), "mask"), (ge, torch.int32, (T, M, K, K), "ge")):
+        if t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise ValueError(f"{what} must be a contiguous {dt} tensor {shape} (got {tuple(t.shape)} {t.dtype})")
+    launched(model_lib().spadot_ligrec_count(_p(S0), _p(S), _p(wk), _p(pairs), int(pair_range[0]), int(pair_range[1]), _p(mask), T,
+                                             M, ns, K, L, int(skip), _p(ge), _stream()),
+             "spadot_ligrec_count", f"K <= {LIGREC_MAX_K}, pairs inside the {ns} selected genes")
+    return ge

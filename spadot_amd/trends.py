@@ -35,6 +35,7 @@ import time
 
 import numpy as np
 
+from ._call import launched, ptr as _p, stream as _stream
 from .markers import TARGET_SUM, bh_adjust, load_marker_counts
 from .utils._preprocess_utils import RawCounts, load_counts
 
@@ -45,21 +46,10 @@ DRIVER_KEYS = ("r", "pval", "padj", "n_valid")
 DRIVER_COLUMNS = ("gene", "fate", "r", "pval", "padj")
 
 
-def _stream():
-    import ctypes
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
-    return t.data_ptr()
-
-
 def _check(rc, name):
     if rc == -7:
         raise ValueError(f"{name}: W must have 1 .. {MAX_COLUMNS} columns and at most {MAX_ROWS} rows")
-    if rc != 0:
-        raise RuntimeError(f"{name} failed with code {rc}")
+    launched(rc, name)
 
 
 def lognorm_values(dc):
@@ -70,9 +60,8 @@ def lognorm_values(dc):
     total = dc.row_total(mask)
     nnz = int(dc.cval.numel())
     values = torch.empty(nnz, dtype=torch.float32, device=dc.device)
-    rc = model_lib().spadot_mk_lognorm(_p(dc.ridx), _p(dc.cval), _p(total), nnz, TARGET_SUM, _p(values), _stream())
-    if rc != 0:
-        raise RuntimeError(f"spadot_mk_lognorm failed with code {rc}")
+    launched(model_lib().spadot_mk_lognorm(_p(dc.ridx), _p(dc.cval), _p(total), nnz, TARGET_SUM, _p(values), _stream()),
+             "spadot_mk_lognorm")
     return values
 
 

@@ -10,7 +10,7 @@ import autocorr_ref as ref
 import nhood_cases as nc
 
 SEED = nc.SEED
-GS, THREADS = 2, 1024                          # the library's genes per group and workgroup (spadot_amd.ops.AUTOCORR_*)
+GS, THREADS = 2, 1024                          # the library's genes per group and workgroup (spadot_amd.stage_ops.AUTOCORR_*)
 PLANTED_GENES = ("gradient", "marker", "noise_a", "noise_b", "checkerboard", "single")
 PLANTED_PERMS = 200
 U = 2.0 ** -53

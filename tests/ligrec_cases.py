@@ -12,7 +12,7 @@ import nhood_cases as nc
 from autocorr_cases import csc  # noqa: F401  (the host-side CSC of time points stacked row-wise)
 
 SEED = nc.SEED
-GC, THREADS = 128, 512                         # the library's genes per chunk and workgroup (spadot_amd.ops.LIGREC_*)
+GC, THREADS = 128, 512                         # the library's genes per chunk and workgroup (spadot_amd.stage_ops.LIGREC_*)
 
 
 def values(rng, n, G, density=0.3):

@@ -150,12 +150,12 @@ def test_permuted_labelings_match_the_restatement_from_the_seed_alone(perm_run):
 
 
 def test_the_case_file_holds_the_library_defaults():
-    from spadot_amd import ops
+    from spadot_amd import stage_ops as ops
     assert (cases.GS, cases.THREADS) == (ops.AUTOCORR_GS, ops.AUTOCORR_THREADS)
 
 
 def test_labelings_split_into_runs_that_share_one_scratch_buffer_give_the_same_bits(perm_run, monkeypatch):
-    from spadot_amd import autocorr, ops
+    from spadot_amd import autocorr, stage_ops as ops
     graphs, want, N, D = perm_run
     probs = graphs[1:]                                                               # n = 37 and n = 300, graph indices 0 and 1
     one = _run(probs, 7, lds_limit=0)
@@ -291,7 +291,7 @@ def _desc(n=37, E=150, row0=0, gid=0, lo=0, hi=36):
 
 
 def test_refusals_come_before_any_launch():
-    from spadot_amd import ops
+    from spadot_amd import stage_ops as ops
     from spadot_amd.autocorr import autocorr_sums
     src, dst, V = cases.edge_call()[2]
     dc = Counts([V])

@@ -153,7 +153,7 @@ def _desc(n=37, K=3, B=17, sizes=(20, 0, 17)):
 
 
 def test_refusals_come_before_any_launch():
-    from spadot_amd import ops
+    from spadot_amd import stage_ops as ops
     from spadot_amd.cooccurrence import cooccurrence_counts
     xy, lab, r2, K = cases.edge_call()[2]
     x = _dev(xy)

@@ -241,7 +241,7 @@ def test_the_estimator_follows_sklearns_definitions():
 
 # ---------------------------------------------------------------------------------------------------------------- refusals
 def test_refusals_come_before_any_launch(monkeypatch):
-    from spadot_amd import gmm, ops
+    from spadot_amd import gmm, stage_ops as ops
     # the library's own refusals (-7 -> ValueError): nothing is launched, the outputs keep their fill
     for d, K in ((33, 2), (3, 33), (32, 25)):
         S = gmm._dims(d)[2]

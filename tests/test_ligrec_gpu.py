@@ -193,7 +193,7 @@ def test_permuted_labelings_match_the_restatement_from_the_seed_alone(perm_run):
 
 
 def test_the_case_file_holds_the_library_defaults():
-    from spadot_amd import ops
+    from spadot_amd import stage_ops as ops
     assert (cases.GC, cases.THREADS) == (ops.LIGREC_GC, ops.LIGREC_THREADS) and OTHER_THREADS in (256, 512)
 
 
@@ -226,7 +226,7 @@ def test_a_problem_alone_in_a_batch_run_twice_and_into_a_poisoned_output_gives_t
 
 
 def test_permuting_per_stored_entry_gives_the_same_bits(perm_run):
-    from spadot_amd import ops
+    from spadot_amd import stage_ops as ops
     probs, S, c = perm_run
     need = ops.ligrec_lds_bytes(1025, 7)
     assert need == 8 * 7 * 512 + 1040 and ops.ligrec_lds_bytes(300, 7) < need - 1
@@ -292,7 +292,7 @@ def test_p_values_follow_the_device_sums_and_equal_the_restatement_where_no_tie_
 
 
 def test_refusals_come_before_any_launch():
-    from spadot_amd import ops
+    from spadot_amd import stage_ops as ops
     from spadot_amd.ligrec import ligrec_sums
     V, lab = cases.call4()[2]
     dc = Counts([(V, lab)])

@@ -175,7 +175,7 @@ def _desc(n=37, E=148, K=3, L=3, p0=-1, gid=0):
 
 
 def test_refusals_come_before_any_launch():
-    from spadot_amd import ops
+    from spadot_amd import stage_ops as ops
     from spadot_amd.neighbors import Permuted, nhood_counts
     src, dst, labs, K = cases.edge_call()[2]
     e, lab = _edges(src, dst), _dev(labs)

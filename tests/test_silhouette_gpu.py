@@ -119,7 +119,7 @@ def test_an_undefined_labeling_scores_nan_in_a_batch_and_raises_alone():
 
 
 def test_refusals_come_before_any_launch(monkeypatch):
-    from spadot_amd import ops
+    from spadot_amd import stage_ops as ops
     from spadot_amd.silhouette import silhouette_many, silhouette_samples
     X = _dev(np.zeros((40, 3)))
     valid = (X, torch.tensor([[0, 0, 40, 2]], dtype=torch.int64, device=DEV), torch.arange(40, dtype=torch.int32, device=DEV),

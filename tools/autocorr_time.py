@@ -27,7 +27,6 @@ trends.lognorm_values.  Prints JSON lines:
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -36,6 +35,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from _timing import median, timed  # noqa: E402
 
 
 def synthetic(tps, n, G, density, rng):
@@ -56,14 +57,10 @@ def synthetic(tps, n, G, density, rng):
     return RawCounts(X, np.repeat(np.arange(tps), n), xy, np.arange(G).astype(str))
 
 
-def _median(v):
-    return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
-
-
 def _prepared(edges, dc, values, centre, perms):
     """The tensors and the checked descriptor of one call (as autocorr.autocorr_sums builds them)."""
     import torch
-    from spadot_amd import ops
+    from spadot_amd import stage_ops as ops
     src = torch.cat([s for s, _ in edges])
     dst = torch.cat([d for _, d in edges])
     eoff = np.concatenate([[0], np.cumsum([int(s.shape[0]) for s, _ in edges])])
@@ -76,24 +73,10 @@ def _prepared(edges, dc, values, centre, perms):
 
 
 def _time_launch(prep, G, perms, repeats, threads, gs):
-    import torch
-    from spadot_amd import ops
+    from spadot_amd import stage_ops as ops
     args, checked, out, desc_dev = prep
-
-    def go():
-        ops.autocorr_launch(*args, checked, 0, G, True, 0, perms, 0, None, out, None, threads, gs, desc_dev)
-
-    go()                                                                             # warm: code object
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        go()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return ms
+    return timed(lambda: ops.autocorr_launch(*args, checked, 0, G, True, 0, perms, 0, None, out, None, threads, gs, desc_dev),
+                 repeats)
 
 
 def main():
@@ -112,7 +95,7 @@ def main():
     ap.add_argument("--skip-call", action="store_true")
     a = ap.parse_args()
     import torch
-    from spadot_amd import ops
+    from spadot_amd import stage_ops as ops
     from spadot_amd.autocorr import _moments, autocorr_sums, spatial_autocorr
     from spadot_amd.neighbors import spatial_edges
     from spadot_amd.preprocess import DeviceCounts
@@ -146,14 +129,14 @@ def main():
         for gs in (4, 2):
             rec = dict(what="candidate", shape=shape, threads=threads, gs=gs, edge_terms=terms,
                        default=(threads, gs) == (ops.AUTOCORR_THREADS, ops.AUTOCORR_GS),
-                       **_median(_time_launch(prep, a.genes, a.perms, a.repeats, threads, gs)))
+                       **median(_time_launch(prep, a.genes, a.perms, a.repeats, threads, gs)))
             rec["Gterms_per_s"] = round(terms / (rec["median_ms"] * 1e-3) / 1e9, 2)
             print(json.dumps(rec), flush=True)
     del prep
     none = torch.empty(0, dtype=torch.int32, device=dev)
     prep = _prepared([(none, none)] * dc.T, dc, values, centre, a.perms)
     print(json.dumps(dict(what="prologue", shape=shape + ", no edges", threads=ops.AUTOCORR_THREADS, gs=ops.AUTOCORR_GS,
-                          **_median(_time_launch(prep, a.genes, a.perms, a.repeats, None, None)))), flush=True)
+                          **median(_time_launch(prep, a.genes, a.perms, a.repeats, None, None)))), flush=True)
     del prep
 
     if a.global_genes > 0:
@@ -173,7 +156,7 @@ def main():
             t0 = time.perf_counter()
             res = spatial_autocorr(edges, dc, values, n_perms=a.perms, seed=0)
             call.append((time.perf_counter() - t0) * 1e3)
-        print(json.dumps(dict(what="call", shape=shape, **_median(call))), flush=True)
+        print(json.dumps(dict(what="call", shape=shape, **median(call))), flush=True)
 
     if not a.skip_host:
         import autocorr_ref as ref

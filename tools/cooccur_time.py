@@ -16,7 +16,6 @@ lines:
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -25,6 +24,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from _timing import median, timed  # noqa: E402
 
 
 def synthetic(n, K, rng):
@@ -37,14 +38,10 @@ def synthetic(n, K, rng):
     return xy, lab
 
 
-def _median(v):
-    return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
-
-
 def _prepared(sets, K, radii, dev):
     """The tensors and the checked descriptor of one call (as cooccurrence_counts builds them)."""
     import torch
-    from spadot_amd import ops
+    from spadot_amd import stage_ops as ops
     desc = np.zeros((len(sets), ops.COOCCUR_DESC), dtype=np.int64)
     parts, first = [], 0
     for g, (xy, lab) in enumerate(sets):
@@ -61,19 +58,8 @@ def _prepared(sets, K, radii, dev):
 
 
 def _time_launch(prep, repeats):
-    import torch
-    from spadot_amd import ops
-    ops.cooccur_launch(*prep)                                                   # warm: code object
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        ops.cooccur_launch(*prep)
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return ms
+    from spadot_amd import stage_ops as ops
+    return timed(lambda: ops.cooccur_launch(*prep), repeats)
 
 
 def main():
@@ -96,7 +82,7 @@ def main():
     shape = f"{a.tps} x {a.n} spots, K = {a.domains}, B = {a.bins}"
     tests = a.tps * a.n * (a.n - 1) * a.bins
 
-    rec = dict(what="launch", shape=shape, pair_threshold_tests=tests, **_median(_time_launch(_prepared(sets, a.domains, radii, dev),
+    rec = dict(what="launch", shape=shape, pair_threshold_tests=tests, **median(_time_launch(_prepared(sets, a.domains, radii, dev),
                                                                                               a.repeats)))
     rec["Gtests_per_s"] = round(tests / (rec["median_ms"] * 1e-3) / 1e9, 2)
     print(json.dumps(rec), flush=True)
@@ -108,7 +94,7 @@ def main():
         t0 = time.perf_counter()
         res = cooccurrence(coords, labs, radii=radii, n_clusters=[a.domains] * a.tps)
         call.append((time.perf_counter() - t0) * 1e3)
-    print(json.dumps(dict(what="call", shape=shape, **_median(call))), flush=True)
+    print(json.dumps(dict(what="call", shape=shape, **median(call))), flush=True)
 
     if a.big > 0:
         xy, lab = synthetic(a.big, a.domains, rng)

@@ -28,24 +28,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
+from _timing import median, timed  # noqa: E402
+
 KS = list(range(4, 21))
-
-
-def _median(v):
-    return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
-
-
-def _events(fn, repeats):
-    import torch
-    out = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1))
-    return out
 
 
 def main():
@@ -79,10 +64,10 @@ def main():
     b.em(1, 1e-6, -1.0)                                            # tol < 0: nothing ever stops
     b.estep()
     torch.cuda.synchronize()
-    print(json.dumps(dict(what="m_step", shape=shape, **_median(_events(lambda: b.em(0, 1e-6, -1.0, resp_init=onehot), a.repeats)))),
-          flush=True)
-    print(json.dumps(dict(what="iteration", shape=shape, **_median(_events(lambda: b.em(1, 1e-6, -1.0), a.repeats)))), flush=True)
-    print(json.dumps(dict(what="e_step", shape=shape, **_median(_events(lambda: b.estep(), a.repeats)))), flush=True)
+    m_step = timed(lambda: b.em(0, 1e-6, -1.0, resp_init=onehot), a.repeats, warm=False)
+    print(json.dumps(dict(what="m_step", shape=shape, **median(m_step))), flush=True)
+    print(json.dumps(dict(what="iteration", shape=shape, **median(timed(lambda: b.em(1, 1e-6, -1.0), a.repeats, warm=False)))), flush=True)
+    print(json.dumps(dict(what="e_step", shape=shape, **median(timed(lambda: b.estep(), a.repeats, warm=False)))), flush=True)
     del b, onehot
 
     stages = []
@@ -92,7 +77,7 @@ def main():
         stages.append((time.perf_counter() - t0) * 1e3)
     iters = [r.n_iter_ for rt in res for r in rt]
     print(json.dumps(dict(what="stages", shape=shape, validate_ms=validate_ms, buffers_ms=buffers_ms,
-                          fit_sweep=_median(stages), n_iter_min=min(iters), n_iter_median=int(statistics.median(iters)),
+                          fit_sweep=median(stages), n_iter_min=min(iters), n_iter_median=int(statistics.median(iters)),
                           n_iter_max=max(iters), converged=int(sum(r.converged_ for rt in res for r in rt)))), flush=True)
 
     if not a.skip_host:

@@ -22,7 +22,6 @@ Prints JSON lines:
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -33,24 +32,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-
-def _median(v):
-    return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
-
-
-def _timed(go, repeats):
-    import torch
-    go()                                                                             # warm: code object
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        go()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return ms
+from _timing import median, timed  # noqa: E402
 
 
 def main():
@@ -69,7 +51,7 @@ def main():
     a = ap.parse_args()
     import torch
     from autocorr_time import synthetic
-    from spadot_amd import ops
+    from spadot_amd import stage_ops as ops
     from spadot_amd.ligrec import _device_args, ligrec
     from spadot_amd.preprocess import DeviceCounts
     from spadot_amd.trends import lognorm_values
@@ -97,15 +79,15 @@ def main():
     out = (torch.empty((T, 1 + a.perms, ns, K), dtype=torch.float64, device=dev), torch.empty((T, ns, K), dtype=torch.int32, device=dev))
     for gc in (64, 128, 256):
         for threads in (256, 512):
-            ms = _timed(lambda: ops.ligrec_launch(*args, checked, K, True, 0, a.perms, 0, None, out, threads, gc, desc_dev), a.repeats)
+            ms = timed(lambda: ops.ligrec_launch(*args, checked, K, True, 0, a.perms, 0, None, out, threads, gc, desc_dev), a.repeats)
             rec = dict(what="candidate", shape=shape, threads=threads, gene_chunk=gc, entry_terms=terms,
-                       default=(threads, gc) == (ops.LIGREC_THREADS, ops.LIGREC_GC), **_median(ms))
+                       default=(threads, gc) == (ops.LIGREC_THREADS, ops.LIGREC_GC), **median(ms))
             rec["Gterms_per_s"] = round(terms / (rec["median_ms"] * 1e-3) / 1e9, 2)
             print(json.dumps(rec), flush=True)
     out0 = (torch.empty((T, 1, ns, K), dtype=torch.float64, device=dev), out[1])
-    ms = _timed(lambda: ops.ligrec_launch(*args, checked, K, True, 0, 0, 0, None, out0, None, None, desc_dev), a.repeats)
+    ms = timed(lambda: ops.ligrec_launch(*args, checked, K, True, 0, 0, 0, None, out0, None, None, desc_dev), a.repeats)
     print(json.dumps(dict(what="prologue", shape=shape + ", P = 0", threads=ops.LIGREC_THREADS, gene_chunk=ops.LIGREC_GC,
-                          **_median(ms))), flush=True)
+                          **median(ms))), flush=True)
 
     sizes = np.stack([np.bincount(lab[int(dc.tp_off_host[t]):int(dc.tp_off_host[t + 1])], minlength=K) for t in range(T)])
     wk = torch.as_tensor(1.0 / np.maximum(sizes, 1), device=dev)
@@ -113,8 +95,8 @@ def main():
     mask = torch.ones((T, M, K, K), dtype=torch.uint8, device=dev)
     ge = torch.zeros((T, M, K, K), dtype=torch.int32, device=dev)
     pos = torch.as_tensor(np.searchsorted(sel, pairs).astype(np.int32), device=dev)
-    ms = _timed(lambda: ops.ligrec_count(S0, out[0], wk, pos, (0, ns - 1), mask, 1, ge), a.repeats)
-    print(json.dumps(dict(what="count", shape=shape, comparisons=T * M * K * K * a.perms, **_median(ms))), flush=True)
+    ms = timed(lambda: ops.ligrec_count(S0, out[0], wk, pos, (0, ns - 1), mask, 1, ge), a.repeats)
+    print(json.dumps(dict(what="count", shape=shape, comparisons=T * M * K * K * a.perms, **median(ms))), flush=True)
     S_first = out[0][0, :6].cpu().numpy()
     del out, out0, S0, mask, ge
     torch.cuda.empty_cache()
@@ -125,7 +107,7 @@ def main():
             t0 = time.perf_counter()
             ligrec(dc, lab[np.argsort(dc.perm)], pairs, n_perms=a.perms, seed=0, values=values, timings=launches)
             call.append((time.perf_counter() - t0) * 1e3)
-        print(json.dumps(dict(what="call", shape=shape, launch_ms=[round(v, 3) for v in launches["launch_ms"]], **_median(call))),
+        print(json.dumps(dict(what="call", shape=shape, launch_ms=[round(v, 3) for v in launches["launch_ms"]], **median(call))),
               flush=True)
 
     if not a.skip_host:

@@ -17,7 +17,6 @@ spatial_edges.  Prints JSON lines:
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -26,6 +25,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from _timing import median, timed  # noqa: E402
 
 
 def synthetic(n, K, rng):
@@ -38,14 +39,10 @@ def synthetic(n, K, rng):
     return xy, lab
 
 
-def _median(v):
-    return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
-
-
 def _prepared(edges, labs, K, perms, seed=0):
     """The tensors and the checked descriptor of one enrichment call (as neighbors._run builds them)."""
     import torch
-    from spadot_amd import ops
+    from spadot_amd import stage_ops as ops
     src = torch.cat([s for s, _ in edges])
     dst = torch.cat([d for _, d in edges])
     labels = torch.cat([l.to(torch.uint8) for l in labs])
@@ -62,20 +59,9 @@ def _prepared(edges, labs, K, perms, seed=0):
 
 
 def _time_launch(prep, K, repeats, lds_limit=None):
-    import torch
-    from spadot_amd import ops
+    from spadot_amd import stage_ops as ops
     src, dst, labels, desc, desc_dev, out = prep
-    ops.nhood_launch(src, dst, labels, desc, K, lds_limit, out, desc_dev)      # warm: code object
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        ops.nhood_launch(src, dst, labels, desc, K, lds_limit, out, desc_dev)
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return ms
+    return timed(lambda: ops.nhood_launch(src, dst, labels, desc, K, lds_limit, out, desc_dev), repeats)
 
 
 def main():
@@ -108,7 +94,7 @@ def main():
 
     prep = _prepared(edges, labs, a.domains, a.perms)
     for what, limit in (("launch", None), ("global", 0)):
-        rec = dict(what=what, shape=shape, label_pairs=pairs, **_median(_time_launch(prep, a.domains, a.repeats, limit)))
+        rec = dict(what=what, shape=shape, label_pairs=pairs, **median(_time_launch(prep, a.domains, a.repeats, limit)))
         rec["Gpairs_per_s"] = round(pairs / (rec["median_ms"] * 1e-3) / 1e9, 2)
         print(json.dumps(rec), flush=True)
 
@@ -117,7 +103,7 @@ def main():
         t0 = time.perf_counter()
         res = nhood_enrichment(edges, labs, n_perms=a.perms, seed=0, n_clusters=[a.domains] * a.tps)
         call.append((time.perf_counter() - t0) * 1e3)
-    print(json.dumps(dict(what="call", shape=shape, **_median(call))), flush=True)
+    print(json.dumps(dict(what="call", shape=shape, **median(call))), flush=True)
 
     if a.big > 0:
         xy, lab = synthetic(a.big, a.domains, rng)

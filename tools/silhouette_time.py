@@ -17,7 +17,6 @@ problems.  Prints JSON lines:
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -25,6 +24,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+from _timing import median  # noqa: E402
 
 KS = list(range(4, 21))
 
@@ -43,10 +44,6 @@ def synthetic(tps, n, d, seed=1993):
         Xs.append(x)
         labelings.append(labs)
     return Xs, labelings
-
-
-def _median(v):
-    return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
 
 
 def main():
@@ -86,18 +83,18 @@ def main():
         t0 = time.perf_counter()
         res = batch.results()
         download.append((time.perf_counter() - t0) * 1e3)
-    rec = dict(what="launch", shape=shape, pairs=pairs, **_median(launch))
+    rec = dict(what="launch", shape=shape, pairs=pairs, **median(launch))
     rec["Gpairs_per_s"] = round(pairs / (rec["median_ms"] * 1e-3) / 1e9, 2)
     print(json.dumps(rec), flush=True)
-    print(json.dumps(dict(what="prepare", shape=shape, **_median(prepare))), flush=True)
-    print(json.dumps(dict(what="download", shape=shape, **_median(download))), flush=True)
+    print(json.dumps(dict(what="prepare", shape=shape, **median(prepare))), flush=True)
+    print(json.dumps(dict(what="download", shape=shape, **median(download))), flush=True)
 
     call = []
     for _ in range(max(3, a.repeats // 2)):
         t0 = time.perf_counter()
         res = silhouette_many(Xs, labelings, ncl)
         call.append((time.perf_counter() - t0) * 1e3)
-    print(json.dumps(dict(what="call", shape=shape, **_median(call))), flush=True)
+    print(json.dumps(dict(what="call", shape=shape, **median(call))), flush=True)
 
     if not a.skip_host:
         from sklearn.metrics import silhouette_score
