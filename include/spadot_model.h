@@ -22,6 +22,7 @@
  *   spadot_weighted_moments  no counterpart in the reference: X_csc.T @ W of the log-normalised counts, three moments
  *   spadot_nhood_counts      no counterpart in the reference: the label-pair edge counts of squidpy's gr.nhood_enrichment
  *   spadot_cooccur_counts    no counterpart in the reference: the label-pair counts by distance of squidpy's gr.co_occurrence
+ *   spadot_local_lag         no counterpart in the reference: the neighbour sums and permutation counts of esda's Moran_Local
  *   spadot_autocorr_sums     no counterpart in the reference: the edge sums of squidpy's gr.spatial_autocorr (Moran's I, Geary's C)
  *   spadot_ligrec_*          no counterpart in the reference: the per-domain sums and comparison counts of squidpy's gr.ligrec
  */
@@ -836,6 +837,44 @@ int spadot_ligrec_sums(const long long *colptr, const int *ridx, const float *v,
  * Return -22 for null or inconsistent arguments and -7 outside the limits: K <= 32, T M <= 2147483647, pairs inside 0 .. ns-1. */
 int spadot_ligrec_count(const double *S0, const double *S, const double *wk, const int *pairs, int pair_lo, int pair_hi,
                         const unsigned char *mask, int T, int M, int ns, int K, long long L, int skip, int *ge, void *stream);
+
+/* ---------------------------------------------------------------- local Moran's I (csrc/localmoran.hip)
+ * The neighbour sums behind local Moran's I of every (time point, selected gene, spot) and their comparison with the sums under
+ * conditional permutations, in ONE launch.  Time point t is a CSR over its n spots (rowptr: int32 [n + 1] ascending from 0 to E,
+ * the T arrays back to back; col: int32 [E] out-neighbours in row order, back to back; no self loops expected, duplicates count)
+ * and the rows row0 .. row0 + n - 1 of a CSC matrix (colptr [G + 1] int64, ridx [nnz] int32 ascending inside a column, v [nnz]
+ * fp32).  Gene g of time point t has the value v of its stored entries and 0 elsewhere, and the centre c = centre[t * G + g]
+ * (fp64 [T, G], absolute gene index).  With x the shown values promoted to fp64, the neighbour sum of spot i is
+ *   lag_i = ((0 + (x_j1 - c)) + (x_j2 - c)) + ...      over the row of i in row order (subtractions and additions only).
+ * Observed: x = v.  Permutation p = first .. first + P - 1 shows x_j = v[pi_p(j)], pi_p the permutation of spadot_nhood_counts
+ * under (seed, graph id, p, n), except that while spot i is evaluated the neighbour j* = pi_p^-1(i) shows v[pi_p(i)].  For the
+ * selected genes genes[0 .. ng-1] (int32, any order, repeats allowed; gene_lo, gene_hi: the smallest and the largest) and with
+ * time point t's spot i at column row0 + i of `rows` columns:
+ *   lag[j, row0 + i] = the observed sum (fp64 [ng, rows], written for the spots of the time points)
+ *   ge[j, row0 + i] += #{p : lag^p >= lag^0}     le[j, row0 + i] += #{p : lag^p <= lag^0}      (int32 [ng, rows])
+ * ge and le are ADDED to with integer atomics (exact in any order): the caller zeroes them, and several runs over disjoint
+ * permutations accumulate.  The bits of lag and the integers depend on the row, the gene's values, c and the permutations alone
+ * (two runs, a gene alone, another batch, any threads, gs, perm_chunk, either path: the same).
+ * desc [T, 8] int64, once in host memory (checked here) and once on the device (read by the kernel), per time point:
+ *   0 first entry of col   1 n   2 E   3 row0   4 graph id of the permutation keys   5 first entry of rowptr   6 the smallest
+ *   and 7 the largest entry of col (ignored where E = 0)
+ * ridx_lo, ridx_hi: the smallest and the largest row index in ridx (ignored where nnz = 0).
+ * A workgroup handles one (time point, chunk of perm_chunk permutations, group of gs selected genes): the identity first, then
+ * its permutations.  It keeps a dense fp32 image [n, gs] of the shown values in LDS where 256 + 4 gs n <= lds_limit (at most
+ * 163840; larger values mean 163840), otherwise in scratch.  The observed sums and the counters of its spots live in scratch:
+ * bytes [items, stride] with items = T ceil(P / perm_chunk) ceil(ng / gs) and stride = 16 gs max n + 4 slab, slab = the largest
+ * gs n of the time points whose image does not fit, rounded up to a multiple of 4 (0 if all fit); scratch_bytes: its size.
+ * threads: 256, 512 or 1024 (0: the default, 1024); gs: 2 or 4 (0: the default, 4); perm_chunk >= 1 (0: the default, 128).
+ * Return -22 for null, negative or inconsistent arguments (a scratch buffer that is too small, rows < max(row0 + n) among them)
+ * and -7, before any launch, outside the limits: P >= 1, 1 <= n <= 2147483647, E <= 2147483647, nnz <= 2147483647, every entry of
+ * col in 0 .. n-1, every row index in 0 .. max(row0 + n) - 1, every selected gene in 0 .. G-1, first + P <= 2^32, graph id <=
+ * 2147483647, items <= 2147483647 (gridDim.x), threads and gs as above.  That rowptr ascends from 0 to E is the caller's to
+ * refuse (the kernel clamps what it reads). */
+int spadot_local_lag(const int *rowptr, const int *col, const long long *colptr, const int *ridx, const float *v, long long nnz,
+                     long long ridx_lo, long long ridx_hi, const double *centre, const long long *desc_host,
+                     const long long *desc_dev, int T, int G, const int *genes, int ng, int gene_lo, int gene_hi, long long first,
+                     long long P, long long seed, long long lds_limit, void *scratch, long long scratch_bytes, int threads, int gs,
+                     long long perm_chunk, long long rows, double *lag, int *ge, int *le, void *stream);
 
 /* ---------------------------------------------------------------- trends stage (csrc/trends.hip)
  * The log-normalised counts of every time point, transposed, times a dense row-major fp64 W[n, C] (rows in the permuted order of

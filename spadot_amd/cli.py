@@ -11,6 +11,8 @@
     python -m spadot_amd neighbors --domains CSV [-o DIR] [--prefix P] [--k 6] [--n_perms 1000] [--seed 0] [--device cuda:0]
     python -m spadot_amd cooccurrence --domains CSV [-o DIR] [--prefix P] [--bins 50] [--radius R] [--ring] [--device cuda:0]
     python -m spadot_amd autocorr -i COUNTS [-o DIR] [--prefix P] [--k 6] [--n_perms 100] [--seed 0] [--top 100] [--device cuda:0]
+    python -m spadot_amd hotspots -i COUNTS [-o DIR] [--prefix P] [--k 6] [--n_perms 999] [--seed 0] [--genes A,B | FILE] [--top 50]
+                                  [--alpha 0.05] [--fdr] [--domains CSV] [--device cuda:0]
     python -m spadot_amd ligrec  -i COUNTS --domains CSV --interactions CSV [-o DIR] [--prefix P] [--n_perms 1000] [--seed 0]
                                  [--threshold 0.1] [--top 100] [--device cuda:0]
 
@@ -35,7 +37,10 @@ distance and the co-occurrence ratio, which tells how far an association reaches
 radii instead of those within each (spadot_amd.cooccurrence).  `autocorr` reads the counts and their coordinates: on the
 k-nearest-neighbour graph of every time point, Moran's I and Geary's C of every gene with z-scores and p-values under the analytic
 (normality) null and under random relabelings of the spots: which genes are spatially structured inside a time point, how
-strongly, and with which sign (spadot_amd.autocorr).  `ligrec` reads the counts, the domains table and a csv of
+strongly, and with which sign (spadot_amd.autocorr).  `hotspots` reads the same counts and asks WHERE: local Moran's I
+of every spot for the genes of `--genes` (default: the `--top` genes by Moran's I of every time point), with the quadrant of every
+spot (high-high, low-low or an outlier) and a p-value under conditional permutation; `--domains` also counts the hot and cold
+spots of every gene per domain (spadot_amd.hotspots).  `ligrec` reads the counts, the domains table and a csv of
 ligand-receptor pairs (header `source,target`, gene names): for every time point, every pair and every ordered pair of domains, the
 mean expression of the ligand in the one domain and of the receptor in the other, with a p-value under random relabelings of the
 spots: which domains signal to which, and through which pair (spadot_amd.ligrec)."""
@@ -192,6 +197,35 @@ def build_parser():
                     help="Genes listed per time point in the csv tables, by descending I; 0 lists all. Default: 100")
     ac.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
 
+    hs = sub.add_parser("hotspots", help="Where a gene is spatially structured: local Moran's I of every spot on the "
+                                         "k-nearest-neighbour graph of every time point, with quadrants and a conditional "
+                                         "permutation null.")
+    hs.add_argument("-i", "--data", dest="data", type=str, required=True,
+                    help="The counts: the .npz written by preprocess (its raw counts of the selected genes), or raw counts as "
+                         "preprocess reads them (.npz or .h5ad).")
+    hs.add_argument("-o", "--output_dir", dest="output_dir", type=str,
+                    help="Output directory. Default: the same as where the data locates.")
+    hs.add_argument("--prefix", dest="prefix", type=str, default="", help="Prefix for the hot-spot tables. Default: ''")
+    hs.add_argument("--k", dest="k", type=int, default=6, help="Spatial neighbours per spot. Default: 6")
+    hs.add_argument("--n_perms", dest="n_perms", type=int, default=999,
+                    help="Conditional relabelings of the spots behind p_sim, at least 1. Default: 999")
+    hs.add_argument("--seed", dest="seed", type=int, default=0, help="Seed of the relabelings. Default: 0")
+    hs.add_argument("--genes", dest="genes", type=str,
+                    help="The genes to test: a comma-separated list of names, or a file with one name per line. Default: the "
+                         "--top genes by Moran's I of every time point.")
+    hs.add_argument("--top", dest="top", type=int, default=50,
+                    help="Without --genes: the genes taken per time point by descending Moran's I (their union is tested). "
+                         "Default: 50")
+    hs.add_argument("--alpha", dest="alpha", type=float, default=0.05,
+                    help="A spot is significant where p_sim (folded, as esda's Moran_Local) is at most this. Default: 0.05")
+    hs.add_argument("--fdr", dest="fdr", default=False, action="store_true",
+                    help="Compare the Benjamini-Hochberg adjusted p-value (over the spots of a gene and time point) with --alpha "
+                         "instead.")
+    hs.add_argument("--domains", dest="domains", type=str,
+                    help="The domains.csv written by analyze: also write the significant high-high and low-low spots of every "
+                         "gene per domain.")
+    hs.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
+
     lr = sub.add_parser("ligrec", help="Ligand-receptor tests between the spatial domains of every time point: the mean expression "
                                        "of every pair between every two domains, with a permutation null.")
     lr.add_argument("-i", "--data", dest="data", type=str, required=True,
@@ -292,6 +326,15 @@ def main(argv=None):
             sys.exit(2)
         from .autocorr import autocorr
         autocorr(args)
+    elif args.cmd_choice == "hotspots":
+        named = [("domains table", args.domains)] if args.domains else []
+        for what, path in [("counts", args.data)] + named:
+            if not _exists(path):
+                print(f"SpaDOT hotspots: the {what} does not exist: {path}. Please make sure it is correctly specified.",
+                      file=sys.stderr)
+                sys.exit(2)
+        from .hotspots import hotspots
+        hotspots(args)
     elif args.cmd_choice == "ligrec":
         for what, path in (("counts", args.data), ("domains table", args.domains), ("interactions table", args.interactions)):
             if not _exists(path):

@@ -30,22 +30,6 @@
 #define AC_MAX_ITEMS 2147483647LL  // (time point, labeling, group) triples of one call: gridDim.x
 #define AC_MAX 2147483647LL
 
-// pi^-1 of nh_perm_at: the rounds backwards, walking the same cycle the other way
-__host__ __device__ static inline unsigned ac_perm_inv(const NhPerm &q, unsigned y) {
-    unsigned x = y;
-    do {
-        unsigned L = x >> q.half, R = x & q.mask;
-#pragma unroll
-        for (int r = NH_ROUNDS - 1; r >= 0; --r) {
-            const unsigned t = R ^ (nh_mix32(L ^ q.key[r]) & q.mask);
-            R = L;
-            L = t;
-        }
-        x = (L << q.half) | R;
-    } while (x >= q.n);
-    return x;
-}
-
 template <int GS> struct alignas(4 * GS) AcVec { float v[GS]; };
 
 struct AcItem {

@@ -1,4 +1,4 @@
-// feistel_perm.h -- the permutation pi_p of (seed, graph id, p, n) that the neighbors and autocorr stages share (restated
+// feistel_perm.h -- the permutation pi_p of (seed, graph id, p, n) that the neighbors, autocorr, ligrec and hotspots stages share (restated
 // in numpy in tests/nhood_ref.py): a six-round balanced Feistel network with cycle walking, evaluated per element; no permutation
 // is stored or sorted anywhere.
 #ifndef SPADOT_FEISTEL_PERM_H
@@ -56,6 +56,22 @@ __host__ __device__ static inline unsigned nh_perm_at(const NhPerm &q, unsigned 
             const unsigned t = L ^ (nh_mix32(R ^ q.key[r]) & q.mask);
             L = R;
             R = t;
+        }
+        x = (L << q.half) | R;
+    } while (x >= q.n);
+    return x;
+}
+
+// pi^-1 of nh_perm_at: the rounds backwards, walking the same cycle the other way
+__host__ __device__ static inline unsigned ac_perm_inv(const NhPerm &q, unsigned y) {
+    unsigned x = y;
+    do {
+        unsigned L = x >> q.half, R = x & q.mask;
+#pragma unroll
+        for (int r = NH_ROUNDS - 1; r >= 0; --r) {
+            const unsigned t = R ^ (nh_mix32(L ^ q.key[r]) & q.mask);
+            R = L;
+            L = t;
         }
         x = (L << q.half) | R;
     } while (x >= q.n);

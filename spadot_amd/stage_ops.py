@@ -1,4 +1,4 @@
-"""The launches of the analysis stages (silhouette, gmm, neighbors, cooccurrence, autocorr, ligrec) in libspadot_model.so
+"""The launches of the analysis stages (silhouette, gmm, neighbors, cooccurrence, autocorr, ligrec, hotspots) in libspadot_model.so
 (include/spadot_model.h).  A *_check refuses, before any launch, what the library would refuse or cannot see (ranges that only a
 reduction on the device knows: one host round trip); a *_launch hands over what the check returned.  CPU tensors raise."""
 import ctypes
@@ -534,3 +534,142 @@ def ligrec_count(S0, S, wk, pairs, pair_range, mask, skip, ge):
                                              M, ns, K, L, int(skip), _p(ge), _stream()),
              "spadot_ligrec_count", f"K <= {LIGREC_MAX_K}, pairs inside the {ns} selected genes")
     return ge
+
+
+LOCAL_DESC = 8
+LOCAL_MAX = 2147483647             # spots, edges and stored entries (int32), graph ids, and workgroups of a call (gridDim.x)
+LOCAL_LDS_BYTES = 163840
+LOCAL_LDS_FIXED = 256              # LDS beside the image: the segment bounds
+LOCAL_THREADS = 1024               # the library's defaults (Time)
+LOCAL_GS = 4
+LOCAL_CHUNK = 128
+LOCAL_LIMITS = ("P >= 1 permutations, 1 <= n <= 2147483647 spots and at most 2147483647 edges per time point, at most 2147483647 "
+                "stored entries, every entry of col in 0 .. n-1, every row index inside the time points, every selected gene inside "
+                "the genes, permutation indices below 2^32, at most 2147483647 workgroups per call, threads in (256, 512, 1024), "
+                "gs in (2, 4), perm_chunk >= 1")
+
+
+def local_lds_bytes(n, gs=None):
+    """The LDS bytes a workgroup needs to keep the image of a time point of n spots (the per-spot state lives in global memory:
+    DESIGN 7l)."""
+    return LOCAL_LDS_FIXED + 4 * int(gs or LOCAL_GS) * int(n)
+
+
+def local_scratch_bytes(desc, ng, P, lds_limit=None, gs=None, perm_chunk=None):
+    """The bytes of the scratch buffer of a call (the per-spot state of every workgroup and the images that do not fit in LDS),
+    as the library computes it."""
+    gs, chunk = int(gs or LOCAL_GS), int(perm_chunk or LOCAL_CHUNK)
+    lds_limit = LOCAL_LDS_BYTES if lds_limit is None else min(int(lds_limit), LOCAL_LDS_BYTES)
+    spots = max(int(n) for n in desc[:, 1])
+    slab = max([(gs * int(n) + 3) & ~3 for n in desc[:, 1] if local_lds_bytes(n, gs) > lds_limit] or [0])
+    return int(desc.shape[0]) * -(-int(P) // chunk) * -(-int(ng) // gs) * (16 * gs * spots + 4 * slab)
+
+
+def local_check(rowptr, col, colptr, ridx, values, centre, genes, desc, first, P, threads=None, gs=None, perm_chunk=None):
+    """The refusals of local_lag, before any launch: the limits from the descriptor and the ranges, then per time point the range
+    of col and the order of rowptr, the range of the row indices and of the selected genes and the order of colptr by reductions
+    on the device (one host round trip).  Returns (the descriptor with columns 6 and 7 filled in, the smallest row index, the
+    largest, the smallest selected gene, the largest); ValueError otherwise."""
+    need_cuda(rowptr, col, colptr, ridx, values, centre, genes)
+    desc = _host_desc(desc, LOCAL_DESC, "time point")
+    T = int(desc.shape[0])
+    _typed((rowptr, torch.int32, "rowptr"), (col, torch.int32, "col"), (ridx, torch.int32, "ridx"), (colptr, torch.int64, "colptr"),
+           (values, torch.float32, "values"), (centre, torch.float64, "centre"), (genes, torch.int32, "genes"), any_dim=("centre",))
+    (G, nnz), ng = _csc_sizes(colptr, ridx, values, LOCAL_MAX), int(genes.numel())
+    if tuple(centre.shape) != (T, G):
+        raise ValueError(f"centre must be [T, G] = [{T}, {G}] (got {tuple(centre.shape)})")
+    threads, gs, chunk = int(threads or 0), int(gs or 0), int(perm_chunk or 0)
+    if ng < 1 or threads not in (0, 256, 512, 1024) or gs not in (0, 2, 4) or chunk < 0:
+        raise ValueError(f"spadot_local_lag takes at least one selected gene, threads in (256, 512, 1024), gs in (2, 4) and "
+                         f"perm_chunk >= 1 (got {ng} genes, threads = {threads}, gs = {gs}, perm_chunk = {chunk})")
+    if int(P) < 1:
+        raise ValueError(f"local_lag takes P >= 1 permutations (got P = {int(P)})")
+    _, first, P = _labelings("local_lag", False, first, P)
+    rows = 0
+    for t, (eoff, n, E, row0, gid, roff, _lo, _hi) in enumerate(desc.tolist()):
+        if not 1 <= n <= LOCAL_MAX:
+            raise ValueError(f"time point {t} has {n} spots: spadot_local_lag takes 1 to {LOCAL_MAX} (int32 spot numbers)")
+        if not 0 <= E <= LOCAL_MAX:
+            raise ValueError(f"time point {t} has {E} edges: spadot_local_lag takes at most {LOCAL_MAX} per time point")
+        if eoff < 0 or roff < 0 or not 0 <= row0 <= LOCAL_MAX or not 0 <= gid <= LOCAL_MAX:
+            raise ValueError(f"time point {t}: inconsistent descriptor {desc[t].tolist()}")
+        if eoff + E > col.numel() or roff + n + 1 > rowptr.numel():
+            raise ValueError(f"time point {t}: its rows or edges reach past the end of the tensors")
+        rows = max(rows, row0 + n)
+    if T * -(-P // (chunk or LOCAL_CHUNK)) * -(-ng // (gs or LOCAL_GS)) > LOCAL_MAX:
+        raise ValueError(f"the call holds more than {LOCAL_MAX} workgroups (the grid of one launch)")
+    zero = torch.zeros((), dtype=torch.int64, device=colptr.device)
+    stats = []
+    for eoff, n, E, _row0, _gid, roff, _lo, _hi in desc.tolist():
+        rp = rowptr[roff:roff + n + 1]
+        lo, hi = torch.aminmax(col[eoff:eoff + E]) if E > 0 else (zero, zero)
+        stats += [lo.long(), hi.long(), rp[0].long(), rp[-1].long(), (rp[1:] < rp[:-1]).any().long()]
+    stats += _csc_stats(colptr, ridx, zero) + [s.long() for s in torch.aminmax(genes)]
+    stats = torch.stack(stats).cpu().numpy()                                # the one host round trip ahead of the launch
+    per = stats[:5 * T].reshape(T, 5)
+    desc[:, 6], desc[:, 7] = per[:, 0], per[:, 1]
+    for t in range(T):
+        n, E = int(desc[t, 1]), int(desc[t, 2])
+        if E > 0 and (per[t, 0] < 0 or per[t, 1] >= n):
+            raise ValueError(f"time point {t} has neighbours {int(per[t, 0])} .. {int(per[t, 1])} in col: they must lie in 0 .. "
+                             f"{n - 1}")
+        if per[t, 2] != 0 or per[t, 3] != E or per[t, 4]:
+            raise ValueError(f"the rowptr of time point {t} must ascend from 0 to its {E} edges (it runs from {int(per[t, 2])} to "
+                             f"{int(per[t, 3])})")
+    ridx_lo, ridx_hi, c0, c1, unordered, gene_lo, gene_hi = (int(v) for v in stats[5 * T:])
+    _refuse_rows(ridx_lo, ridx_hi, nnz, rows)
+    if gene_lo < 0 or gene_hi >= G:
+        raise ValueError(f"the selected genes {gene_lo} .. {gene_hi} must lie in 0 .. {G - 1}")
+    _refuse_colptr(c0, c1, unordered, nnz)
+    return desc, ridx_lo, ridx_hi, gene_lo, gene_hi
+
+
+def local_launch(rowptr, col, colptr, ridx, values, centre, genes, checked, first, P, seed=0, lds_limit=None, out=None,
+                 scratch=None, threads=None, gs=None, perm_chunk=None, desc_dev=None):
+    """The launch of local_lag for what local_check has returned (the library checks the descriptor again, on the host).  out:
+    (lag, ge, le) of an earlier launch over the same rows: ge and le are added to (the integers of disjoint runs accumulate
+    exactly), lag is written again with the same bits."""
+    desc, ridx_lo, ridx_hi, gene_lo, gene_hi = checked
+    need_cuda(rowptr, col, colptr, ridx, values, centre, genes, scratch, desc_dev, *(out or ()))
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    T, G, ng = int(desc.shape[0]), int(colptr.numel()) - 1, int(genes.numel())
+    rows = int((desc[:, 3] + desc[:, 1]).max())
+    lds_limit = _lds_limit(lds_limit, LOCAL_LDS_BYTES)
+    threads, gs, chunk = int(threads or 0), int(gs or 0), int(perm_chunk or 0)
+    if threads not in (0, 256, 512, 1024) or gs not in (0, 2, 4) or chunk < 0:    # the library's refusal, ahead of the call
+        launched(-7, "spadot_local_lag", LOCAL_LIMITS)
+    dev = colptr.device
+    if out is None:
+        out = (torch.zeros((ng, rows), dtype=torch.float64, device=dev), torch.zeros((ng, rows), dtype=torch.int32, device=dev),
+               torch.zeros((ng, rows), dtype=torch.int32, device=dev))
+    elif (len(out) != 3 or any(not o.is_contiguous() or tuple(o.shape) != (ng, rows) for o in out)
+          or out[0].dtype != torch.float64 or out[1].dtype != torch.int32 or out[2].dtype != torch.int32):
+        raise ValueError(f"out must be a contiguous float64 and two contiguous int32 tensors [{ng}, {rows}]")
+    need = local_scratch_bytes(desc, ng, P, lds_limit, gs, chunk)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < need:
+        raise ValueError(f"scratch must be a contiguous uint8 tensor of at least {need} bytes")
+    if desc_dev is None:
+        desc_dev = torch.as_tensor(desc, device=dev)
+    rc = model_lib().spadot_local_lag(_p(rowptr), _p(col), _p(colptr), _p(ridx), _p(values), int(ridx.numel()), ridx_lo, ridx_hi,
+                                      _p(centre), _host(desc), _p(desc_dev), T, G, _p(genes), ng, gene_lo, gene_hi, int(first),
+                                      int(P), _signed64(seed), lds_limit, _p(scratch), int(scratch.numel()), threads, gs, chunk,
+                                      rows, _p(out[0]), _p(out[1]), _p(out[2]), _stream())
+    launched(rc, "spadot_local_lag", LOCAL_LIMITS)
+    return out
+
+
+def local_lag(rowptr, col, colptr, ridx, values, centre, genes, desc, first, P, seed=0, lds_limit=None, out=None, scratch=None,
+              threads=None, gs=None, perm_chunk=None):
+    """The observed neighbour sums of local Moran's I and the counts of the conditional permutations whose sum is at least / at
+    most the observed one, for every (selected gene, spot) of every time point in ONE launch (include/spadot_model.h:
+    spadot_local_lag).  rowptr, col int32: the CSR of the time points back to back; colptr int64, ridx int32 and values fp32: the
+    CSC arrays of a DeviceCounts; centre fp64 [T, G]; genes int32: the selected genes; desc: int64 [T, 8] on the host as the
+    header lays it out (columns 6 and 7, the range of col, are filled in here).  Permutations first .. first + P - 1 under seed.
+    lds_limit: the LDS bytes a workgroup may use (default and at most 163840); a time point whose image does not fit keeps it in
+    `scratch` (allocated here when not given).  Returns (lag fp64, ge int32, le int32), device tensors [genes, rows].
+    ValueError, before any launch, outside the limits; RuntimeError for a CPU tensor."""
+    checked = local_check(rowptr, col, colptr, ridx, values, centre, genes, desc, first, P, threads, gs, perm_chunk)
+    return local_launch(rowptr, col, colptr, ridx, values, centre, genes, checked, first, P, seed, lds_limit, out, scratch, threads,
+                        gs, perm_chunk)
