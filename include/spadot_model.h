@@ -23,6 +23,7 @@
  *   spadot_nhood_counts      no counterpart in the reference: the label-pair edge counts of squidpy's gr.nhood_enrichment
  *   spadot_cooccur_counts    no counterpart in the reference: the label-pair counts by distance of squidpy's gr.co_occurrence
  *   spadot_local_lag         no counterpart in the reference: the neighbour sums and permutation counts of esda's Moran_Local
+ *   spadot_cross_*           no counterpart in the reference: the cross sums of a bivariate Moran's I between genes (esda's Moran_BV)
  *   spadot_autocorr_sums     no counterpart in the reference: the edge sums of squidpy's gr.spatial_autocorr (Moran's I, Geary's C)
  *   spadot_ligrec_*          no counterpart in the reference: the per-domain sums and comparison counts of squidpy's gr.ligrec
  */
@@ -875,6 +876,40 @@ int spadot_local_lag(const int *rowptr, const int *col, const long long *colptr,
                      const long long *desc_dev, int T, int G, const int *genes, int ng, int gene_lo, int gene_hi, long long first,
                      long long P, long long seed, long long lds_limit, void *scratch, long long scratch_bytes, int threads, int gs,
                      long long perm_chunk, long long rows, double *lag, int *ge, int *le, void *stream);
+
+/* ---------------------------------------------------------------- bivariate Moran's I (csrc/crossmoran.hip)
+ * The cross sums of every pair of selected genes of every time point, observed and under relabelings of the spots.  Both entries
+ * work on two dense fp64 images Z and Y [zrows, GP], GP = ng rounded up to a multiple of 16, in which time point t owns the rows
+ * zoff .. zoff + npad - 1, npad = n rounded up to a multiple of 4.  With gene j = genes[j] of the CSC of spadot_local_lag, its
+ * fp32 values v (0 where nothing is stored) and the centre c = centre[t * G + genes[j]]:
+ *   Z[zoff + i, j] = (double)v_i - c                                   (0.0 in the rows i >= n and the columns j >= ng)
+ *   Y[zoff + i, j] = ((0 + Z[zoff + j1, j]) + Z[zoff + j2, j]) + ...   over the row of i in the CSR, in row order
+ * (subtractions and additions only: Y has the bits of the lag of spadot_local_lag).
+ * desc [T, 9] int64, once in host memory (checked here) and once on the device (read by the kernels), per time point:
+ *   0 first entry of col   1 n   2 E   3 row0   4 graph id of the permutation keys   5 first entry of rowptr   6 the smallest
+ *   and 7 the largest entry of col (ignored where E = 0)   8 zoff
+ * spadot_cross_dense(): writes Z (fill, then the stored entries: no atomics) and Y.  With colptr NULL, Z is the caller's (dense
+ * columns: the padding must be zero) and only Y is written; ridx, v, centre and genes are not read then.  rowptr, col, colptr,
+ * ridx, v, nnz, ridx_lo, ridx_hi, genes, gene_lo, gene_hi as in spadot_local_lag.
+ * spadot_cross_sums(): for the labelings l = 0 .. observed + P - 1 (the identity first if observed, then the permutations first ..
+ * first + P - 1 of spadot_nhood_counts under (seed, graph id, p, n)):
+ *   M[t, l, g, h] = sum_i Z[zoff + pi_l(i), g] Y[zoff + i, h]        (fp64 [T, observed + P, ng, ng])
+ * on the fp64 matrix cores.  One workgroup of 256 threads per (t, l, 64 x 64 tile of M); every wavefront runs over all the spots
+ * of the time point in ascending order, four per v_mfma_f64_16x16x4_f64, so the bits of an element depend on n, its two columns
+ * and the permutation alone (two runs, a pair alone, another batch, another split over `first`: the same).  No permuted copy of Z
+ * is made; LDS: 1 KiB of permuted spot numbers.
+ * Return -22 for null, negative or inconsistent arguments (n < 1, ng < 1, GP other than ng rounded up to 16, rows of a time
+ * point outside zrows among them) and -7, before any launch, outside the limits: ng <= 4096, n, E, nnz, row0 and graph id <=
+ * 2147483647, first + P <= 2^32, T (observed + P) ceil(ng / 64)^2 <= 2147483647 (gridDim.x) for the sums; T <= 65535 (gridDim.y),
+ * ceil(max npad GP / 256) <= 2147483647, every entry of col in 0 .. n-1, every row index in 0 .. max(row0 + n) - 1 and every
+ * selected gene in 0 .. G-1 for the images. */
+int spadot_cross_dense(const int *rowptr, const int *col, const long long *colptr, const int *ridx, const float *v, long long nnz,
+                       long long ridx_lo, long long ridx_hi, const double *centre, const long long *desc_host,
+                       const long long *desc_dev, int T, int G, const int *genes, int ng, int gene_lo, int gene_hi, int GP,
+                       long long zrows, double *Z, double *Y, void *stream);
+int spadot_cross_sums(const double *Z, const double *Y, long long zrows, int GP, const long long *desc_host,
+                      const long long *desc_dev, int T, int ng, int observed, long long first, long long P, long long seed,
+                      double *M, void *stream);
 
 /* ---------------------------------------------------------------- trends stage (csrc/trends.hip)
  * The log-normalised counts of every time point, transposed, times a dense row-major fp64 W[n, C] (rows in the permuted order of

@@ -286,6 +286,8 @@ def model_lib():
         "spadot_ligrec_count": [vp, vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, ll, ci, vp, vp],
         "spadot_local_lag": [vp, vp, vp, vp, vp, ll, ll, ll, vp, vp, vp, ci, ci, vp, ci, ci, ci, ll, ll, ll, ll, vp, ll, ci, ci, ll,
                              ll, vp, vp, vp, vp],
+        "spadot_cross_dense": [vp, vp, vp, vp, vp, ll, ll, ll, vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, ll, vp, vp, vp],
+        "spadot_cross_sums": [vp, vp, ll, ci, vp, vp, ci, ci, ci, ll, ll, ll, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)

@@ -13,6 +13,8 @@
     python -m spadot_amd autocorr -i COUNTS [-o DIR] [--prefix P] [--k 6] [--n_perms 100] [--seed 0] [--top 100] [--device cuda:0]
     python -m spadot_amd hotspots -i COUNTS [-o DIR] [--prefix P] [--k 6] [--n_perms 999] [--seed 0] [--genes A,B | FILE] [--top 50]
                                   [--alpha 0.05] [--fdr] [--domains CSV] [--device cuda:0]
+    python -m spadot_amd modules -i COUNTS [-o DIR] [--prefix P] [--k 6] [--n_perms 100] [--seed 0] [--genes A,B | FILE] [--top 100]
+                                 [--min_sim 0.15] [--min_genes 2] [--alpha 0.05] [--top_pairs 0] [--device cuda:0]
     python -m spadot_amd ligrec  -i COUNTS --domains CSV --interactions CSV [-o DIR] [--prefix P] [--n_perms 1000] [--seed 0]
                                  [--threshold 0.1] [--top 100] [--device cuda:0]
 
@@ -40,7 +42,10 @@ k-nearest-neighbour graph of every time point, Moran's I and Geary's C of every 
 strongly, and with which sign (spadot_amd.autocorr).  `hotspots` reads the same counts and asks WHERE: local Moran's I
 of every spot for the genes of `--genes` (default: the `--top` genes by Moran's I of every time point), with the quadrant of every
 spot (high-high, low-low or an outlier) and a p-value under conditional permutation; `--domains` also counts the hot and cold
-spots of every gene per domain (spadot_amd.hotspots).  `ligrec` reads the counts, the domains table and a csv of
+spots of every gene per domain (spadot_amd.hotspots).  `modules` reads the same counts and asks WHICH of those genes go
+together: the bivariate Moran's I of every pair of the selected genes with a p-value under random relabelings, the spatial gene
+modules that average linkage cuts out of it, a score of every module in every spot and the overlap of the modules of consecutive
+time points (spadot_amd.modules).  `ligrec` reads the counts, the domains table and a csv of
 ligand-receptor pairs (header `source,target`, gene names): for every time point, every pair and every ordered pair of domains, the
 mean expression of the ligand in the one domain and of the receptor in the other, with a p-value under random relabelings of the
 spots: which domains signal to which, and through which pair (spadot_amd.ligrec)."""
@@ -226,6 +231,37 @@ def build_parser():
                          "gene per domain.")
     hs.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
 
+    mo = sub.add_parser("modules", help="Which spatially structured genes go together: the bivariate Moran's I of every pair of "
+                                        "selected genes on the k-nearest-neighbour graph of every time point, with a "
+                                        "permutation null, and the spatial gene modules cut out of it.")
+    mo.add_argument("-i", "--data", dest="data", type=str, required=True,
+                    help="The counts: the .npz written by preprocess (its raw counts of the selected genes), or raw counts as "
+                         "preprocess reads them (.npz or .h5ad).")
+    mo.add_argument("-o", "--output_dir", dest="output_dir", type=str,
+                    help="Output directory. Default: the same as where the data locates.")
+    mo.add_argument("--prefix", dest="prefix", type=str, default="", help="Prefix for the module tables. Default: ''")
+    mo.add_argument("--k", dest="k", type=int, default=6, help="Spatial neighbours per spot. Default: 6")
+    mo.add_argument("--n_perms", dest="n_perms", type=int, default=100,
+                    help="Random relabelings of the spots behind z_sim and p_sim, at least 1. Default: 100")
+    mo.add_argument("--seed", dest="seed", type=int, default=0, help="Seed of the relabelings. Default: 0")
+    mo.add_argument("--genes", dest="genes", type=str,
+                    help="The genes to group: a comma-separated list of names, or a file with one name per line. Default: the "
+                         "--top genes by Moran's I of every time point.")
+    mo.add_argument("--top", dest="top", type=int, default=100,
+                    help="Without --genes: the genes taken per time point by descending Moran's I (their union is grouped). "
+                         "Default: 100")
+    mo.add_argument("--min_sim", dest="min_sim", type=float, default=0.15,
+                    help="Average-linkage clusters are cut where the mean bivariate Moran's I between them falls below this. "
+                         "Default: 0.15")
+    mo.add_argument("--min_genes", dest="min_genes", type=int, default=2,
+                    help="A cluster of fewer genes is no module (label -1). Default: 2")
+    mo.add_argument("--alpha", dest="alpha", type=float, default=0.05,
+                    help="The pairs with a Benjamini-Hochberg adjusted p-value of at most this are counted in the summary. "
+                         "Default: 0.05")
+    mo.add_argument("--top_pairs", dest="top_pairs", type=int, default=0,
+                    help="Pairs listed per time point in the pair tables, by descending |R|; 0 lists all. Default: 0")
+    mo.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
+
     lr = sub.add_parser("ligrec", help="Ligand-receptor tests between the spatial domains of every time point: the mean expression "
                                        "of every pair between every two domains, with a permutation null.")
     lr.add_argument("-i", "--data", dest="data", type=str, required=True,
@@ -335,6 +371,13 @@ def main(argv=None):
                 sys.exit(2)
         from .hotspots import hotspots
         hotspots(args)
+    elif args.cmd_choice == "modules":
+        if not _exists(args.data):
+            print(f"SpaDOT modules: the counts do not exist: {args.data}. Please make sure they are correctly specified.",
+                  file=sys.stderr)
+            sys.exit(2)
+        from .modules import modules
+        modules(args)
     elif args.cmd_choice == "ligrec":
         for what, path in (("counts", args.data), ("domains table", args.domains), ("interactions table", args.interactions)):
             if not _exists(path):

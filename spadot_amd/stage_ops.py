@@ -1,5 +1,5 @@
-"""The launches of the analysis stages (silhouette, gmm, neighbors, cooccurrence, autocorr, ligrec, hotspots) in libspadot_model.so
-(include/spadot_model.h).  A *_check refuses, before any launch, what the library would refuse or cannot see (ranges that only a
+"""The launches of the analysis stages (silhouette, gmm, neighbors, cooccurrence, autocorr, ligrec, hotspots, modules) in
+libspadot_model.so (include/spadot_model.h).  A *_check refuses, before any launch, what the library would refuse or cannot see (ranges that only a
 reduction on the device knows: one host round trip); a *_launch hands over what the check returned.  CPU tensors raise."""
 import ctypes
 
@@ -673,3 +673,198 @@ def local_lag(rowptr, col, colptr, ridx, values, centre, genes, desc, first, P, 
     checked = local_check(rowptr, col, colptr, ridx, values, centre, genes, desc, first, P, threads, gs, perm_chunk)
     return local_launch(rowptr, col, colptr, ridx, values, centre, genes, checked, first, P, seed, lds_limit, out, scratch, threads,
                         gs, perm_chunk)
+
+
+CROSS_DESC = 9
+CROSS_MAX = 2147483647             # spots, edges and stored entries (int32), graph ids, and workgroups of a call (gridDim.x)
+CROSS_MAX_G = 4096                 # selected genes of a call
+CROSS_MAX_T = 65535                # time points of the images (gridDim.y)
+CROSS_TILE = 64                    # rows and columns of M per workgroup
+CROSS_LIMITS = ("1 <= G <= 4096 selected genes, 1 <= n <= 2147483647 spots and at most 2147483647 edges per time point, at most "
+                "2147483647 stored entries, every entry of col in 0 .. n-1, every row index inside the time points, every selected "
+                "gene inside the genes, permutation indices below 2^32, at most 65535 time points and 2147483647 workgroups per "
+                "call")
+
+
+def cross_padded(ng):
+    """The columns of the images of a call over ng selected genes."""
+    return (int(ng) + 15) // 16 * 16
+
+
+def cross_layout(sizes):
+    """(zoff int64 [T], zrows): the first row of every time point in the images, n rounded up to a multiple of 4 each."""
+    pad = (np.asarray(sizes, dtype=np.int64) + 3) // 4 * 4
+    zoff = np.concatenate([[0], np.cumsum(pad)]).astype(np.int64)
+    return zoff[:-1], int(zoff[-1])
+
+
+def _cross_desc(desc, ng, name):
+    """The limits that the descriptor and the number of selected genes decide.  Returns (desc, zrows needed)."""
+    desc = _host_desc(desc, CROSS_DESC, "time point")
+    ng = int(ng)
+    if not 1 <= ng <= CROSS_MAX_G:
+        raise ValueError(f"{name} takes 1 to {CROSS_MAX_G} selected genes (got {ng})")
+    need = 0
+    for t, (eoff, n, E, row0, gid, roff, _lo, _hi, zoff) in enumerate(desc.tolist()):
+        if not 1 <= n <= CROSS_MAX:
+            raise ValueError(f"time point {t} has {n} spots: {name} takes 1 to {CROSS_MAX} (int32 spot numbers)")
+        if not 0 <= E <= CROSS_MAX:
+            raise ValueError(f"time point {t} has {E} edges: {name} takes at most {CROSS_MAX} per time point")
+        if eoff < 0 or roff < 0 or zoff < 0 or not 0 <= row0 <= CROSS_MAX or not 0 <= gid <= CROSS_MAX:
+            raise ValueError(f"time point {t}: inconsistent descriptor {desc[t].tolist()}")
+        need = max(need, zoff + (n + 3) // 4 * 4)
+    return desc, need
+
+
+def _cross_image(t, what, zrows, GP):
+    if t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != (zrows, GP):
+        raise ValueError(f"{what} must be a contiguous float64 tensor [{zrows}, {GP}] (got {tuple(t.shape)} {t.dtype})")
+
+
+def cross_dense_check(rowptr, col, colptr, ridx, values, centre, genes, desc, Z=None):
+    """The refusals of cross_dense, before any launch: the limits from the descriptor, then per time point the range of col and
+    the order of rowptr and, with a CSC, the range of the row indices and of the selected genes and the order of colptr by
+    reductions on the device (one host round trip).  colptr None: the dense columns, Z [zrows, GP] is the caller's and genes the
+    number of its columns.  Returns (the descriptor with columns 6 and 7 filled in, the smallest row index, the largest, the
+    smallest selected gene, the largest, ng); ValueError otherwise."""
+    csc = colptr is not None
+    need_cuda(rowptr, col, Z, *((colptr, ridx, values, centre, genes) if csc else ()))
+    ng = int(genes.numel()) if csc else int(genes)
+    desc, need = _cross_desc(desc, ng, "spadot_cross_dense")
+    T = int(desc.shape[0])
+    if T > CROSS_MAX_T:
+        raise ValueError(f"the call holds {T} time points: spadot_cross_dense takes at most {CROSS_MAX_T} (the grid of one launch)")
+    _typed((rowptr, torch.int32, "rowptr"), (col, torch.int32, "col"))
+    G = nnz = 0
+    if csc:
+        _typed((ridx, torch.int32, "ridx"), (colptr, torch.int64, "colptr"), (values, torch.float32, "values"),
+               (centre, torch.float64, "centre"), (genes, torch.int32, "genes"), any_dim=("centre",))
+        G, nnz = _csc_sizes(colptr, ridx, values, CROSS_MAX)
+        if tuple(centre.shape) != (T, G):
+            raise ValueError(f"centre must be [T, G] = [{T}, {G}] (got {tuple(centre.shape)})")
+    elif Z is None:
+        raise ValueError("without a CSC, cross_dense takes the image Z of the dense columns")
+    if Z is not None:
+        _cross_image(Z, "Z", int(Z.shape[0]) if Z.dim() == 2 else -1, cross_padded(ng))
+        if Z.shape[0] < need:
+            raise ValueError(f"Z holds {int(Z.shape[0])} rows: the time points need {need}")
+    rows = 0
+    for t, (eoff, n, E, row0, _gid, roff, _lo, _hi, _zoff) in enumerate(desc.tolist()):
+        if eoff + E > col.numel() or roff + n + 1 > rowptr.numel():
+            raise ValueError(f"time point {t}: its rows or edges reach past the end of the tensors")
+        rows = max(rows, row0 + n)
+    if -(-need * cross_padded(ng) // 256) > CROSS_MAX:
+        raise ValueError(f"the images hold more than {CROSS_MAX} workgroups of 256 cells (the grid of one launch)")
+    zero = torch.zeros((), dtype=torch.int64, device=rowptr.device)
+    stats = []
+    for eoff, n, E, _row0, _gid, roff, _lo, _hi, _zoff in desc.tolist():
+        rp = rowptr[roff:roff + n + 1]
+        lo, hi = torch.aminmax(col[eoff:eoff + E]) if E > 0 else (zero, zero)
+        stats += [lo.long(), hi.long(), rp[0].long(), rp[-1].long(), (rp[1:] < rp[:-1]).any().long()]
+    if csc:
+        stats += _csc_stats(colptr, ridx, zero) + [s.long() for s in torch.aminmax(genes)]
+    stats = torch.stack(stats).cpu().numpy()                                # the one host round trip ahead of the launch
+    per = stats[:5 * T].reshape(T, 5)
+    desc[:, 6], desc[:, 7] = per[:, 0], per[:, 1]
+    for t in range(T):
+        n, E = int(desc[t, 1]), int(desc[t, 2])
+        if E > 0 and (per[t, 0] < 0 or per[t, 1] >= n):
+            raise ValueError(f"time point {t} has neighbours {int(per[t, 0])} .. {int(per[t, 1])} in col: they must lie in 0 .. "
+                             f"{n - 1}")
+        if per[t, 2] != 0 or per[t, 3] != E or per[t, 4]:
+            raise ValueError(f"the rowptr of time point {t} must ascend from 0 to its {E} edges (it runs from {int(per[t, 2])} to "
+                             f"{int(per[t, 3])})")
+    ridx_lo = ridx_hi = gene_lo = gene_hi = 0
+    if csc:
+        ridx_lo, ridx_hi, c0, c1, unordered, gene_lo, gene_hi = (int(v) for v in stats[5 * T:])
+        _refuse_rows(ridx_lo, ridx_hi, nnz, rows)
+        if gene_lo < 0 or gene_hi >= G:
+            raise ValueError(f"the selected genes {gene_lo} .. {gene_hi} must lie in 0 .. {G - 1}")
+        _refuse_colptr(c0, c1, unordered, nnz)
+    return desc, ridx_lo, ridx_hi, gene_lo, gene_hi, ng
+
+
+def cross_dense_launch(rowptr, col, colptr, ridx, values, centre, genes, checked, Z=None, out=None, desc_dev=None):
+    """The launch of cross_dense for what cross_dense_check has returned (the library checks the descriptor again, on the
+    host).  Returns (Z, Y)."""
+    desc, ridx_lo, ridx_hi, gene_lo, gene_hi, ng = checked
+    csc = colptr is not None
+    need_cuda(rowptr, col, Z, desc_dev, *((colptr, ridx, values, centre, genes) if csc else ()), *(out or ()))
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    T, GP = int(desc.shape[0]), cross_padded(ng)
+    need = int((desc[:, 8] + (desc[:, 1] + 3) // 4 * 4).max())
+    dev = rowptr.device
+    if out is not None:
+        if len(out) != 2 or (not csc and out[0] is not Z):
+            raise ValueError("out is the pair (Z, Y); with dense columns its Z is the image that was given")
+        Z, Y = out
+    else:
+        Z = torch.empty((need, GP), dtype=torch.float64, device=dev) if csc else Z
+        Y = torch.empty((int(Z.shape[0]), GP), dtype=torch.float64, device=dev)
+    zrows = int(Z.shape[0]) if Z.dim() == 2 else -1
+    _cross_image(Z, "Z", zrows, GP)
+    _cross_image(Y, "Y", zrows, GP)
+    if zrows < need:
+        raise ValueError(f"the images hold {zrows} rows: the time points need {need}")
+    if desc_dev is None:
+        desc_dev = torch.as_tensor(desc, device=dev)
+    G = int(colptr.numel()) - 1 if csc else 0
+    rc = model_lib().spadot_cross_dense(_p(rowptr), _p(col), _p(colptr) if csc else None, _p(ridx) if csc else None,
+                                        _p(values) if csc else None, int(ridx.numel()) if csc else 0, ridx_lo, ridx_hi,
+                                        _p(centre) if csc else None, _host(desc), _p(desc_dev), T, G, _p(genes) if csc else None,
+                                        ng, gene_lo, gene_hi, GP, zrows, _p(Z), _p(Y), _stream())
+    launched(rc, "spadot_cross_dense", CROSS_LIMITS)
+    return Z, Y
+
+
+def cross_dense(rowptr, col, colptr, ridx, values, centre, genes, desc, Z=None, out=None):
+    """The centred dense image Z of the selected genes and its neighbour sums Y (include/spadot_model.h: spadot_cross_dense), fp64
+    device tensors [zrows, GP].  rowptr, col int32: the CSR of the time points back to back; colptr int64, ridx int32 and values
+    fp32: the CSC arrays of a DeviceCounts; centre fp64 [T, G]; genes int32: the selected genes (any order, repeats allowed);
+    desc: int64 [T, 9] on the host as the header lays it out (columns 6 and 7, the range of col, are filled in here; column 8
+    from cross_layout).  Dense columns: colptr, ridx, values, centre None, genes the number of columns and Z their image.
+    ValueError, before any launch, outside the limits; RuntimeError for a CPU tensor."""
+    checked = cross_dense_check(rowptr, col, colptr, ridx, values, centre, genes, desc, Z)
+    return cross_dense_launch(rowptr, col, colptr, ridx, values, centre, genes, checked, Z, out)
+
+
+def cross_check(Z, Y, desc, ng, observed, first, P):
+    """The refusals of cross_sums, before any launch: all of them follow from the descriptor and the shapes.  Returns the
+    descriptor; ValueError otherwise."""
+    need_cuda(Z, Y)
+    desc, need = _cross_desc(desc, ng, "spadot_cross_sums")
+    observed, first, P = _labelings("cross_sums", observed, first, P)
+    zrows = int(Z.shape[0]) if Z.dim() == 2 else -1
+    _cross_image(Z, "Z", zrows, cross_padded(ng))
+    _cross_image(Y, "Y", zrows, cross_padded(ng))
+    if zrows < need:
+        raise ValueError(f"the images hold {zrows} rows: the time points need {need}")
+    if int(desc.shape[0]) * (observed + P) * (-(-int(ng) // CROSS_TILE)) ** 2 > CROSS_MAX:
+        raise ValueError(f"the call holds more than {CROSS_MAX} workgroups (the grid of one launch)")
+    return desc
+
+
+def cross_launch(Z, Y, checked, ng, observed, first, P, seed=0, out=None, desc_dev=None):
+    """The launch of cross_sums for what cross_check has returned (the library checks the descriptor again, on the host)."""
+    need_cuda(Z, Y, out, desc_dev)
+    desc = np.ascontiguousarray(checked, dtype=np.int64)
+    T, ng, L = int(desc.shape[0]), int(ng), int(bool(observed)) + int(P)
+    if out is None:
+        out = torch.empty((T, L, ng, ng), dtype=torch.float64, device=Z.device)
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != T * L * ng * ng:
+        raise ValueError(f"out must be a contiguous float64 tensor of {T} x {L} x {ng} x {ng} values")
+    if desc_dev is None:
+        desc_dev = torch.as_tensor(desc, device=Z.device)
+    rc = model_lib().spadot_cross_sums(_p(Z), _p(Y), int(Z.shape[0]), cross_padded(ng), _host(desc), _p(desc_dev), T, ng,
+                                       int(bool(observed)), int(first), int(P), _signed64(seed), _p(out), _stream())
+    launched(rc, "spadot_cross_sums", CROSS_LIMITS)
+    return out
+
+
+def cross_sums(Z, Y, desc, ng, observed, first, P, seed=0, out=None):
+    """The cross sums M[t, l, g, h] = sum_i Z[pi_l(i), g] Y[i, h] of every pair of the ng selected genes of every (time point,
+    labeling) in ONE launch on the fp64 matrix cores (include/spadot_model.h: spadot_cross_sums).  Z, Y: the images of
+    cross_dense; desc: the same descriptor.  Labelings: the identity (observed) and the permutations first .. first + P - 1 under
+    seed.  Returns M, an fp64 device tensor [T, observed + P, ng, ng] (out: the tensor to write into).  ValueError, before any
+    launch, outside the limits; RuntimeError for a CPU tensor."""
+    return cross_launch(Z, Y, cross_check(Z, Y, desc, ng, observed, first, P), ng, observed, first, P, seed, out)
