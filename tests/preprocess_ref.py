@@ -124,14 +124,21 @@ def sparkx(counts, location):
                 selected=keep_gene[order[:n_keep]])
 
 
-def normalize_log_scale(counts, target=1e-4, clip=None):
-    """_preprocess_utils.py:31-49 on one time point: normalize_total(target_sum) over the given columns, log1p, scale (ddof
-    1, std 0 -> 1), fp64; clip: symmetric clip after scaling (None: none)."""
+def log_stats(counts, target=1e-4):
+    """normalize_total(target_sum) over the given columns and log1p on one time point, fp64 dense: (v, mean, std with ddof 1
+    and std 0 -> 1; a single row has std 0 as well, not numpy's NaN)."""
     x = np.asarray(sp.csr_matrix(counts, dtype=np.float64).todense())
     tot = x.sum(1, keepdims=True)
     v = np.log1p(np.divide(x * target, tot, out=np.zeros_like(x), where=tot > 0))
     mu = v.mean(0)
-    sd = v.std(0, ddof=1)
+    sd = v.std(0, ddof=1) if v.shape[0] > 1 else np.zeros(v.shape[1])
     sd[sd == 0] = 1
+    return v, mu, sd
+
+
+def normalize_log_scale(counts, target=1e-4, clip=None):
+    """_preprocess_utils.py:31-49 on one time point: normalize_total(target_sum) over the given columns, log1p, scale (ddof
+    1, std 0 -> 1), fp64; clip: symmetric clip after scaling (None: none)."""
+    v, mu, sd = log_stats(counts, target)
     z = (v - mu) / sd
     return np.clip(z, -clip, clip) if clip else z

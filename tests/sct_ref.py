@@ -48,8 +48,9 @@ def step1_set(lg, n_genes=2000, seed=1448145):
 
 
 # ---------------------------------------------------------------- qpois_reg + theta_ml (sctransform_utils.py:88-187)
-def fit_poisson(Y, x, tol=1e-9, maxiters=100):
-    """All rows of Y at once.  Returns (coefficients [G, 2] = b_new, fitted mu [G, N], iterations [G])."""
+def fit_poisson(Y, x, tol=1e-9, maxiters=100, full=False):
+    """All rows of Y at once.  Returns (coefficients [G, 2] = b_new, fitted mu [G, N], iterations [G]); with full also the
+    coefficients [G, 2] that the fitted mu was computed from (those before the last update)."""
     G, N = Y.shape
     X = np.stack([np.ones(N), x], axis=1)
     b = np.zeros((G, 2))
@@ -58,6 +59,7 @@ def fit_poisson(Y, x, tol=1e-9, maxiters=100):
     dif = np.ones(G)
     ij = np.full(G, 2)
     m_last = np.zeros((G, N))
+    b_last = np.zeros((G, 2))
     iters = np.zeros(G, dtype=np.int64)
     while active.any():
         a = np.flatnonzero(active)
@@ -68,15 +70,17 @@ def fit_poisson(Y, x, tol=1e-9, maxiters=100):
         step = np.einsum("gij,gj->gi", np.linalg.inv(L2), L1)
         bn = b[a] + step
         dif[a] = np.abs(bn - b[a]).sum(1)
+        b_last[a] = b[a]
         b[a] = bn
         m_last[a] = m
         iters[a] += 1
         ij[a] += 1
         active[a] = (dif[a] > tol) & (ij[a] != maxiters)
-    return b, m_last, iters
+    return (b, m_last, iters, b_last) if full else (b, m_last, iters)
 
 
-def theta_ml(Y, mu, limit=10, eps=0.0001220703):
+def theta_ml(Y, mu, limit=10, eps=0.0001220703, full=False):
+    """theta [G]; with full also the iterations taken [G]."""
     G, N = Y.shape
     t0 = N / ((Y / mu - 1) ** 2).sum(1)
     it = np.ones(G, dtype=np.int64)
@@ -93,7 +97,15 @@ def theta_ml(Y, mu, limit=10, eps=0.0001220703):
         t0[a] = th[:, 0] + de[a]
         it[a] += 1
         active[a] = (it[a] < limit) & (np.abs(de[a]) > eps)
-    return np.where(t0 < 0, 0.0, t0)
+    theta = np.where(t0 < 0, 0.0, t0)
+    return (theta, it - 1) if full else theta
+
+
+def pearson_residuals(Y, x, pars):
+    """pearson_residual (sctransform_utils.py:17-37) without a clip: Y [G, N], x = log10 umi [N], pars [G, 3] rows of
+    (theta, b0, b1); mu = exp(b0 + b1 x), r = (y - mu) / sqrt(mu + mu^2 / theta)."""
+    mu = np.exp(pars[:, 1:2] + pars[:, 2:3] * x[None, :])
+    return (Y - mu) / np.sqrt(mu + mu ** 2 / pars[:, :1])
 
 
 # ---------------------------------------------------------------- bw.SJ (bw.py), loops as written there
