@@ -22,6 +22,7 @@
  *   spadot_weighted_moments  no counterpart in the reference: X_csc.T @ W of the log-normalised counts, three moments
  *   spadot_nhood_counts      no counterpart in the reference: the label-pair edge counts of squidpy's gr.nhood_enrichment
  *   spadot_cooccur_counts    no counterpart in the reference: the label-pair counts by distance of squidpy's gr.co_occurrence
+ *   spadot_ripley_*          no counterpart in the reference: the pair, nearest-neighbour and empty-space counts of squidpy's gr.ripley
  *   spadot_local_lag         no counterpart in the reference: the neighbour sums and permutation counts of esda's Moran_Local
  *   spadot_cross_*           no counterpart in the reference: the cross sums of a bivariate Moran's I between genes (esda's Moran_BV)
  *   spadot_autocorr_sums     no counterpart in the reference: the edge sums of squidpy's gr.spatial_autocorr (Moran's I, Geary's C)
@@ -761,6 +762,48 @@ int spadot_nhood_counts(const int *src, const int *dst, const unsigned char *lab
  * refuse (the labels never reach the library: the offsets do). */
 int spadot_cooccur_counts(const double *xy, const long long *desc_host, const long long *desc_dev, const double *r2_host,
                           const double *r2_dev, int P, int K_max, int B_max, long long *out, void *stream);
+
+/* ---------------------------------------------------------------- Ripley's L, G and F per domain (csrc/ripley.hip)
+ * The integers behind Ripley's functions of every (problem, domain, pattern) of a call in ONE counting launch; the definition
+ * is restated in numpy in tests/ripley_ref.py.  Domain c of a problem holds n_c spots and 1 + S patterns of n_c points each:
+ * pattern 0 its own spots; pattern s >= 1, under null 0 ("labels"), the spots that receive label c under the permutation of
+ * spadot_nhood_counts with (seed, g, s - 1, n) acting on the sorted positions (point i is xy[pi^-1(off_c + i)]), under null 1
+ * ("csr") the points 0 .. n_c - 1 of stream 1 + c S + s - 1 generated in the window.  Stream 0 holds the M probe points.  Per
+ * pattern and threshold t, with d2 the unfused squared distance of spadot_cooccur_counts:
+ *   stat 0  Lc = #{ordered pairs i != j of the pattern : d2 <= r2[t]}
+ *   stat 1  Gc = #{points of the pattern whose nearest other point has d2 <= r2[t]}   (a lone point is never counted)
+ *   stat 2  Fc = #{probe points whose nearest point of the pattern has d2 <= r2[t]}
+ * A generated point is a pure function of (seed, g, stream, i): key = splitmix(seed ^ (g << 32) ^ stream) ^ 0x52504C5953494D31,
+ * w_j = splitmix(key + (3 i + j) 0x9E3779B97F4A7C15), u_j = (w_j >> 11) 2^-53; the triangle is the first k with
+ * fl(u_0 cum[V - 3]) < cum[k] (the last where there is none); where u_1 + u_2 > 1 both are replaced by 1 - u; the point is
+ * (A + u_1 (B - A)) + u_2 (C - A) with (A, B, C) = (V0, V_{k+1}, V_{k+2}), every operation rounded once.
+ * xy: fp64 [sum n, 2], per problem its spots ORDERED BY (label, index), the problems back to back.  desc [P, 48] int64, once in
+ * host memory (checked here) and once on the device (read by the kernel), per problem:
+ *   0 first spot in xy (checked)   1 n   2 K   3 B   4 S   5 M   6 null (0 labels, 1 csr)   7 modes (1 L | 2 G | 4 F)
+ *   8 g   9 first row of its window in hull / cum   10 V, the window's vertices   11 0
+ *   12 .. 12 + K   the cluster offsets (desc[12] = 0, desc[12 + K] = n)
+ * r2 [P, BP] fp64 as for spadot_cooccur_counts (padded with -1.0), on the host and on the device.  hull [hull_rows, 2] fp64: the
+ * windows' vertices, counter-clockwise; cum [hull_rows] fp64: beside the first V - 2 vertices of a window the cumulative areas
+ * of its fan triangles (V0, V_{k+1}, V_{k+2}) (a sliver whose area rounding makes negative counts 0: cum never descends), then
+ * two places that are not read; both on the host and on the device.
+ * out: int64 [P, K_max, 1 + S_max, 3, B_max], problem p in its corner [K, 1 + S, 3, B], written completely (zeros too; a
+ * statistic outside `modes` stays zero).  Integers only reach memory: a problem gives the same integers alone, in any batch,
+ * run after run, under a larger K_max, S_max or B_max.
+ * Return -22 for null or inconsistent arguments (a window that turns right, goes round more than once, has fewer than 3
+ * vertices, non-finite coordinates or descending areas among them) and -7, before any launch, outside the limits:
+ * 1 <= K <= K_max <= 32, 1 <= B <= B_max <= 64, 1 <= S <= S_max <= 9999, 1 <= M <= 1048576, V <= 256, 1 <= n <= 2147483391,
+ * P <= 65535 (gridDim.z), K (1 + S) <= 65535 (gridDim.y), thresholds as for spadot_cooccur_counts.  Non-finite coordinates
+ * are the caller's to refuse. */
+int spadot_ripley_counts(const double *xy, const long long *desc_host, const long long *desc_dev, const double *r2_host,
+                         const double *r2_dev, const double *hull_host, const double *hull_dev, const double *cum_host,
+                         const double *cum_dev, long long hull_rows, int P, int K_max, int S_max, int B_max, long long seed,
+                         long long *out, void *stream);
+
+/* The points 0 .. count - 1 of stream `stream_id` of problem g under seed, generated in one window by the device function that
+ * spadot_ripley_counts uses: hull [V, 2] and cum [V - 2] on the host (checked as above) and on the device, out fp64 [count, 2].
+ * Return -22 / -7 as above; 1 <= count <= 2147483391, 0 <= stream_id <= 1 + 32 * 9999. */
+int spadot_ripley_points(const double *hull_host, const double *hull_dev, const double *cum_host, const double *cum_dev, int V,
+                         long long seed, long long g, long long stream_id, long long count, double *out, void *stream);
 
 /* ---------------------------------------------------------------- spatial autocorrelation (csrc/autocorr.hip)
  * The two edge sums behind Moran's I and Geary's C of every (time point, gene, labeling) in ONE launch.  Time point t is a

@@ -17,6 +17,8 @@
                                  [--min_sim 0.15] [--min_genes 2] [--alpha 0.05] [--top_pairs 0] [--device cuda:0]
     python -m spadot_amd ligrec  -i COUNTS --domains CSV --interactions CSV [-o DIR] [--prefix P] [--n_perms 1000] [--seed 0]
                                  [--threshold 0.1] [--top 100] [--device cuda:0]
+    python -m spadot_amd ripley --domains CSV [-o DIR] [--prefix P] [--bins 50] [--radius R] [--n_sim 99] [--n_probes 1000]
+                                [--null labels|csr] [--mode L,G,F] [--window hull|box] [--alpha 0.05] [--seed 0] [--device cuda:0]
 
 `preprocess` runs SPARK-X feature selection and the scaling on the device (spadot_amd.preprocess).  The balancing rule's gene
 clusters come from K-means by default; `--gene_clusters louvain` clusters SCTransform Pearson residuals with Louvain as the
@@ -48,7 +50,13 @@ modules that average linkage cuts out of it, a score of every module in every sp
 time points (spadot_amd.modules).  `ligrec` reads the counts, the domains table and a csv of
 ligand-receptor pairs (header `source,target`, gene names): for every time point, every pair and every ordered pair of domains, the
 mean expression of the ligand in the one domain and of the receptor in the other, with a p-value under random relabelings of the
-spots: which domains signal to which, and through which pair (spadot_amd.ligrec)."""
+spots: which domains signal to which, and through which pair (spadot_amd.ligrec).  `ripley` reads the domains table and
+looks at every domain on its own: Ripley's L (pairs of its spots by radius), G (the distance from a spot to the nearest spot of
+its domain) and F (the distance from random probe points to the domain) over the radii of `cooccurrence`, each against an
+envelope of `--n_sim` simulated patterns of the same size -- by default the domain's label dealt out at random over the spots
+(`--null labels`, the right null on a lattice of spots), or points uniform in the window (`--null csr`, squidpy's) -- with
+pointwise p-values, a global envelope test per domain and a verdict `clustered`, `dispersed` or `random` (spadot_amd.ripley,
+DESIGN 7n)."""
 import argparse
 import os
 import sys
@@ -185,6 +193,31 @@ def build_parser():
     co.add_argument("--ring", dest="ring", default=False, action="store_true",
                     help="Ratios of the pairs between consecutive radii (annuli) instead of within each radius (discs).")
     co.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
+
+    rp = sub.add_parser("ripley", help="Ripley's L, G and F of every spatial domain on its own, against a Monte-Carlo envelope: "
+                                       "one territory, scattered islands, or no different from chance, and at which scale.")
+    rp.add_argument("--domains", dest="domains", type=str, required=True,
+                    help="The domains.csv written by analyze: row, timepoint, kmeans, pixel_x, pixel_y.")
+    rp.add_argument("-o", "--output_dir", dest="output_dir", type=str,
+                    help="Output directory. Default: the same as where the domains table locates.")
+    rp.add_argument("--prefix", dest="prefix", type=str, default="", help="Prefix for the ripley tables. Default: ''")
+    rp.add_argument("--bins", dest="bins", type=int, default=50, help="Radii per time point, 1 to 64. Default: 50")
+    rp.add_argument("--radius", dest="radius", type=float,
+                    help="The largest radius, in the units of pixel_x / pixel_y. Default: per time point, a quarter of the "
+                         "diagonal of the spots' bounding box.")
+    rp.add_argument("--n_sim", dest="n_sim", type=int, default=99, help="Simulated patterns per domain, 1 to 9999. Default: 99")
+    rp.add_argument("--n_probes", dest="n_probes", type=int, default=1000,
+                    help="Probe points per time point behind F, 1 to 1048576. Default: 1000")
+    rp.add_argument("--null", dest="null", type=str, default="labels", choices=["labels", "csr"],
+                    help="The simulated patterns: the domain's label dealt out at random over the spots (labels), or points "
+                         "uniform in the window (csr). Default: labels")
+    rp.add_argument("--mode", dest="mode", type=str, default="L,G,F", help="The statistics to count, of L, G and F. Default: L,G,F")
+    rp.add_argument("--window", dest="window", type=str, default="hull", choices=["hull", "box"],
+                    help="The window: the convex hull of a time point's spots, or their bounding box. Default: hull")
+    rp.add_argument("--alpha", dest="alpha", type=float, default=0.05,
+                    help="Level of the global envelope test behind the `pattern` column. Default: 0.05")
+    rp.add_argument("--seed", dest="seed", type=int, default=0, help="Seed of the simulations and the probe points. Default: 0")
+    rp.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
 
     ac = sub.add_parser("autocorr", help="Spatial autocorrelation of every gene inside every time point: Moran's I and Geary's C "
                                          "on the k-nearest-neighbour graph, with an analytic and a permutation null.")
@@ -355,6 +388,13 @@ def main(argv=None):
             sys.exit(2)
         from .cooccurrence import cooccur
         cooccur(args)
+    elif args.cmd_choice == "ripley":
+        if not _exists(args.domains):
+            print(f"SpaDOT ripley: the domains table does not exist: {args.domains}. Please make sure it is correctly "
+                  "specified.", file=sys.stderr)
+            sys.exit(2)
+        from .ripley import ripley_stage
+        ripley_stage(args)
     elif args.cmd_choice == "autocorr":
         if not _exists(args.data):
             print(f"SpaDOT autocorr: the counts do not exist: {args.data}. Please make sure they are correctly specified.",

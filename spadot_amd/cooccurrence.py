@@ -115,36 +115,16 @@ def _squares(radii, g):
     return r * r
 
 
-def cooccurrence_counts(coords, labels, radii=None, radii_sq=None, n_clusters=None, out=None):
-    """coords[g]: the fp64 [n, 2] device tensor of problem g; labels[g]: its integer labeling (numpy or torch); radii[g] its
-    radii in the units of the coordinates, or radii_sq[g] their squares (exactly one of the two); n_clusters[g]: its K (default:
-    its largest label + 1).  One call to the library for all problems; returns [g] -> int64 numpy [K, K, B].  ValueError /
-    RuntimeError before any launch; out: an int64 device tensor [P, K_max, K_max, B_max] to write into."""
+def sorted_problems(coords, labels, n_clusters=None, no_cpu=NO_CPU):
+    """What the stages that count by distance refuse about the spots and the labelings of a call, before any launch, and the
+    layout they hand to the device.  Returns (the device, xy fp64 [sum n, 2] with every problem's spots ordered by (label,
+    index), [g] -> K, int64 [P, 32] domain sizes); one host round trip."""
     import torch
-    from . import stage_ops as ops
-    if (radii is None) == (radii_sq is None):
-        raise ValueError("cooccurrence_counts takes exactly one of radii and radii_sq")
-    given = radii if radii is not None else radii_sq
     P = len(coords)
-    if P < 1 or len(labels) != P or len(given) != P:
-        raise ValueError(f"cooccurrence_counts takes one labeling and one set of radii per problem ({P} problems, {len(labels)} "
-                         f"labelings, {len(given)} sets of radii)")
-    if n_clusters is not None and len(n_clusters) != P:
-        raise ValueError(f"n_clusters holds {len(n_clusters)} cluster counts for {P} problems")
-    if P > MAX_PROBLEMS:
-        raise ValueError(f"the call holds {P} problems: the device takes at most {MAX_PROBLEMS} per call")
-    r2 = []
-    for g, r in enumerate(given):
-        t = _squares(r, g) if radii is not None else np.asarray(r, dtype=np.float64).reshape(-1)
-        r2.append(t)                                     # two radii that differ may still have one square: checked as squares too
-        if not 1 <= t.shape[0] <= MAX_BINS:
-            raise ValueError(f"problem {g} has {t.shape[0]} thresholds: the device takes 1 to {MAX_BINS}")
-        if not np.all(np.isfinite(t)) or np.any(t < 0) or np.any(np.diff(t) <= 0):
-            raise ValueError(f"the squared thresholds of problem {g} must be finite, >= 0 and strictly increasing")
     dev, xs, labs = None, [], []
     for g, (xy, lab) in enumerate(zip(coords, labels)):
         if not isinstance(xy, torch.Tensor) or not xy.is_cuda:
-            raise RuntimeError(NO_CPU.format("the coordinates of problem %d are not a device tensor" % g))
+            raise RuntimeError(no_cpu.format("the coordinates of problem %d are not a device tensor" % g))
         if xy.dim() != 2 or xy.shape[1] != 2 or xy.shape[0] < 1 or not xy.dtype.is_floating_point:
             raise ValueError(f"the coordinates of problem {g} must form a floating-point [n, 2] block of at least one spot "
                              f"(got {tuple(xy.shape)} {xy.dtype})")
@@ -178,16 +158,47 @@ def cooccurrence_counts(coords, labels, radii=None, radii_sq=None, n_clusters=No
             if not finite:
                 raise ValueError(f"problem {g} holds coordinates that are not finite")
             Ks.append(K)
+        # the spots of every problem by (label, index): a stable sort of the labels
+        xy = torch.cat([x[torch.sort(lab, stable=True)[1]] for x, lab in zip(xs, labs)]).contiguous()
+    return dev, xy, Ks, stats[:, 3:]
+
+
+def cooccurrence_counts(coords, labels, radii=None, radii_sq=None, n_clusters=None, out=None):
+    """coords[g]: the fp64 [n, 2] device tensor of problem g; labels[g]: its integer labeling (numpy or torch); radii[g] its
+    radii in the units of the coordinates, or radii_sq[g] their squares (exactly one of the two); n_clusters[g]: its K (default:
+    its largest label + 1).  One call to the library for all problems; returns [g] -> int64 numpy [K, K, B].  ValueError /
+    RuntimeError before any launch; out: an int64 device tensor [P, K_max, K_max, B_max] to write into."""
+    import torch
+    from . import stage_ops as ops
+    if (radii is None) == (radii_sq is None):
+        raise ValueError("cooccurrence_counts takes exactly one of radii and radii_sq")
+    given = radii if radii is not None else radii_sq
+    P = len(coords)
+    if P < 1 or len(labels) != P or len(given) != P:
+        raise ValueError(f"cooccurrence_counts takes one labeling and one set of radii per problem ({P} problems, {len(labels)} "
+                         f"labelings, {len(given)} sets of radii)")
+    if n_clusters is not None and len(n_clusters) != P:
+        raise ValueError(f"n_clusters holds {len(n_clusters)} cluster counts for {P} problems")
+    if P > MAX_PROBLEMS:
+        raise ValueError(f"the call holds {P} problems: the device takes at most {MAX_PROBLEMS} per call")
+    r2 = []
+    for g, r in enumerate(given):
+        t = _squares(r, g) if radii is not None else np.asarray(r, dtype=np.float64).reshape(-1)
+        r2.append(t)                                     # two radii that differ may still have one square: checked as squares too
+        if not 1 <= t.shape[0] <= MAX_BINS:
+            raise ValueError(f"problem {g} has {t.shape[0]} thresholds: the device takes 1 to {MAX_BINS}")
+        if not np.all(np.isfinite(t)) or np.any(t < 0) or np.any(np.diff(t) <= 0):
+            raise ValueError(f"the squared thresholds of problem {g} must be finite, >= 0 and strictly increasing")
+    dev, xy, Ks, sizes = sorted_problems(coords, labels, n_clusters)
+    with torch.cuda.device(dev):
         desc = np.zeros((P, ops.COOCCUR_DESC), dtype=np.int64)
         first = 0
         for g in range(P):
-            n = int(xs[g].shape[0])
+            n = int(sizes[g].sum())
             desc[g, :4] = (first, n, Ks[g], r2[g].shape[0])
-            desc[g, 5:5 + Ks[g]] = np.cumsum(stats[g, 3:3 + Ks[g]])
+            desc[g, 5:5 + Ks[g]] = np.cumsum(sizes[g, :Ks[g]])
             first += n
         K_max, B_max = max(Ks), max(t.shape[0] for t in r2)
-        # the spots of every problem by (label, index): a stable sort of the labels
-        xy = torch.cat([x[torch.sort(lab, stable=True)[1]] for x, lab in zip(xs, labs)]).contiguous()
         res = ops.cooccur_counts(xy, desc, r2, K_max, B_max, out=out).cpu().numpy()
     return [np.ascontiguousarray(res[g, :Ks[g], :Ks[g], :r2[g].shape[0]]) for g in range(P)]
 

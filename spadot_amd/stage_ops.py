@@ -1,4 +1,4 @@
-"""The launches of the analysis stages (silhouette, gmm, neighbors, cooccurrence, autocorr, ligrec, hotspots, modules) in
+"""The launches of the analysis stages (silhouette, gmm, neighbors, cooccurrence, autocorr, ligrec, hotspots, modules, ripley) in
 libspadot_model.so (include/spadot_model.h).  A *_check refuses, before any launch, what the library would refuse or cannot see (ranges that only a
 reduction on the device knows: one host round trip); a *_launch hands over what the check returned.  CPU tensors raise."""
 import ctypes
@@ -868,3 +868,157 @@ def cross_sums(Z, Y, desc, ng, observed, first, P, seed=0, out=None):
     seed.  Returns M, an fp64 device tensor [T, observed + P, ng, ng] (out: the tensor to write into).  ValueError, before any
     launch, outside the limits; RuntimeError for a CPU tensor."""
     return cross_launch(Z, Y, cross_check(Z, Y, desc, ng, observed, first, P), ng, observed, first, P, seed, out)
+
+
+RIPLEY_MAX_K = 32
+RIPLEY_MAX_B = 64
+RIPLEY_MAX_S = 9999                # simulations of a problem
+RIPLEY_MAX_M = 1048576             # probe points of a problem
+RIPLEY_MAX_V = 256                 # vertices of a window (LDS)
+RIPLEY_MAX_N = COOCCUR_MAX_N
+RIPLEY_MAX_P = 65535               # problems of a call (gridDim.z)
+RIPLEY_MAX_Y = 65535               # patterns of a problem, K (1 + S) (gridDim.y)
+RIPLEY_MAX_G = 2147483647          # problem numbers, as the graph ids of spadot_nhood_counts
+RIPLEY_MAX_STREAM = 1 + RIPLEY_MAX_K * RIPLEY_MAX_S
+RIPLEY_DESC = 48
+RIPLEY_MODES = {"L": 1, "G": 2, "F": 4}
+RIPLEY_LIMITS = ("1 <= K <= 32 label values, 1 <= B <= 64 thresholds that are finite, >= 0 and strictly increasing, 1 <= S <= 9999 "
+                 "simulations, 1 <= M <= 1048576 probe points, a window of at most 256 vertices, 1 <= n <= 2147483391 spots per "
+                 "problem, at most 65535 problems per call and K (1 + S) <= 65535 patterns per problem")
+
+
+def ripley_window(vertices, cum, what="the window"):
+    """(vertices fp64 [V, 2], cum fp64 [V - 2]) as the library accepts them: 3 to 256 finite vertices that never turn right and go
+    round once, ascending areas >= 0.  ValueError otherwise."""
+    v = np.ascontiguousarray(vertices, dtype=np.float64)
+    c = np.ascontiguousarray(cum, dtype=np.float64).reshape(-1)
+    if v.ndim != 2 or v.shape[1] != 2 or v.shape[0] < 3 or c.shape[0] != v.shape[0] - 2:
+        raise ValueError(f"{what} must hold V >= 3 vertices [V, 2] and V - 2 cumulative areas (got {v.shape} and {c.shape})")
+    if v.shape[0] > RIPLEY_MAX_V:
+        raise ValueError(f"{what} has {v.shape[0]} vertices: the device takes at most {RIPLEY_MAX_V} (window=\"box\" has four)")
+    if not np.all(np.isfinite(v)) or not np.all(np.isfinite(c)):
+        raise ValueError(f"{what} holds vertices or areas that are not finite")
+    e = np.roll(v, -1, axis=0) - v
+    f = np.roll(e, -1, axis=0)
+    if np.any(e[:, 0] * f[:, 1] < e[:, 1] * f[:, 0]):
+        raise ValueError(f"{what} must be convex with its vertices counter-clockwise (it turns right somewhere)")
+    for s in (np.sign(e[:, 0]), np.sign(e[:, 1])):
+        s = s[s != 0]
+        if s.size and np.count_nonzero(s != np.roll(s, 1)) > 2:
+            raise ValueError(f"{what} must be convex with its vertices counter-clockwise (it goes round more than once)")
+    if np.any(c < 0) or np.any(np.diff(c) < 0):
+        raise ValueError(f"the cumulative areas of {what} must be >= 0 and ascend")
+    return v, c
+
+
+def ripley_check(xy, desc, r2, windows, K_max, S_max, B_max):
+    """The refusals of ripley_counts that the descriptor, the thresholds and the windows decide, before any launch.  windows[p]:
+    (vertices [V, 2], cum [V - 2]) of problem p on the host.  Returns (desc int64 [P, 48] with columns 9 and 10 filled in, r2 fp64
+    [P, BP] padded with -1.0, hull fp64 [rows, 2], cum fp64 [rows]); ValueError otherwise."""
+    need_cuda(xy)
+    desc = _host_desc(desc, RIPLEY_DESC, "problem")
+    K_max, S_max, B_max, P = int(K_max), int(S_max), int(B_max), desc.shape[0]
+    if not 1 <= K_max <= RIPLEY_MAX_K:
+        raise ValueError(f"spadot_ripley_counts takes 1 to {RIPLEY_MAX_K} label values (got K_max = {K_max})")
+    if not 1 <= B_max <= RIPLEY_MAX_B:
+        raise ValueError(f"spadot_ripley_counts takes 1 to {RIPLEY_MAX_B} thresholds (got B_max = {B_max})")
+    if not 1 <= S_max <= RIPLEY_MAX_S:
+        raise ValueError(f"spadot_ripley_counts takes 1 to {RIPLEY_MAX_S} simulations (got S_max = {S_max})")
+    if P > RIPLEY_MAX_P:
+        raise ValueError(f"the call holds {P} problems: spadot_ripley_counts takes at most {RIPLEY_MAX_P} (the grid of one launch)")
+    if len(r2) != P or len(windows) != P:
+        raise ValueError(f"the call holds {P} problems, {len(r2)} sets of thresholds and {len(windows)} windows")
+    BP = cooccur_padded(B_max)
+    pad = np.full((P, BP), -1.0, dtype=np.float64)
+    first, rows, hulls, cums = 0, 0, [], []
+    for p, row in enumerate(desc.tolist()):
+        off, n, K, B, S, M, null, modes, g = row[:9]
+        if not 1 <= K <= K_max:
+            raise ValueError(f"problem {p} has {K} label values: spadot_ripley_counts takes 1 to {K_max} here, at most {RIPLEY_MAX_K}")
+        if not 1 <= B <= B_max:
+            raise ValueError(f"problem {p} has {B} thresholds: spadot_ripley_counts takes 1 to {B_max} here, at most {RIPLEY_MAX_B}")
+        if not 1 <= S <= S_max:
+            raise ValueError(f"problem {p} has {S} simulations: spadot_ripley_counts takes 1 to {S_max} here, at most {RIPLEY_MAX_S}")
+        if not 1 <= M <= RIPLEY_MAX_M:
+            raise ValueError(f"problem {p} has {M} probe points: spadot_ripley_counts takes 1 to {RIPLEY_MAX_M}")
+        if not 1 <= n <= RIPLEY_MAX_N:
+            raise ValueError(f"problem {p} has {n} spots: spadot_ripley_counts takes 1 to {RIPLEY_MAX_N} (int32 positions)")
+        if K * (1 + S) > RIPLEY_MAX_Y:
+            raise ValueError(f"problem {p} has {K} x {1 + S} patterns: spadot_ripley_counts takes at most {RIPLEY_MAX_Y} per problem "
+                             f"(the grid of one launch)")
+        coff = row[12:13 + K]
+        if (off != first or coff[0] != 0 or coff[-1] != n or any(hi < lo for lo, hi in zip(coff, coff[1:])) or null not in (0, 1)
+                or not 1 <= modes <= 7 or not 0 <= g <= RIPLEY_MAX_G):
+            raise ValueError(f"problem {p}: inconsistent descriptor {row[:13 + K]}")
+        first += n
+        t = np.asarray(r2[p], dtype=np.float64).reshape(-1)
+        if t.shape[0] == BP and np.all(t[B:] == -1.0):
+            t = t[:B]
+        if t.shape[0] != B:
+            raise ValueError(f"problem {p} has {t.shape[0]} thresholds and its descriptor says {B}")
+        if not np.all(np.isfinite(t)) or np.any(t < 0) or np.any(np.diff(t) <= 0):
+            raise ValueError(f"the squared thresholds of problem {p} must be finite, >= 0 and strictly increasing")
+        pad[p, :B] = t
+        v, c = ripley_window(*windows[p], what=f"the window of problem {p}")
+        desc[p, 9], desc[p, 10], desc[p, 11] = rows, v.shape[0], 0
+        hulls.append(v)
+        cums.append(np.concatenate([c, [0.0, 0.0]]))
+        rows += v.shape[0]
+    if xy.dtype != torch.float64 or xy.dim() != 2 or xy.shape[1] != 2 or not xy.is_contiguous() or xy.shape[0] != first:
+        raise ValueError(f"xy must be a contiguous fp64 [{first}, 2] tensor (got {tuple(xy.shape)} {xy.dtype})")
+    return desc, pad, np.ascontiguousarray(np.concatenate(hulls)), np.ascontiguousarray(np.concatenate(cums))
+
+
+def ripley_launch(xy, checked, K_max, S_max, B_max, seed=0, out=None):
+    """The launch of ripley_counts for what ripley_check has returned (the library checks all of it again, on the host)."""
+    desc, r2, hull, cum = checked
+    need_cuda(xy, out)
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    r2, hull, cum = (np.ascontiguousarray(a, dtype=np.float64) for a in (r2, hull, cum))
+    K_max, S_max, B_max, P = int(K_max), int(S_max), int(B_max), int(desc.shape[0])
+    size = P * K_max * (1 + S_max) * 3 * B_max
+    if out is None:
+        out = torch.empty((P, K_max, 1 + S_max, 3, B_max), dtype=torch.int64, device=xy.device)
+    elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != size:
+        raise ValueError(f"out must be a contiguous int64 tensor of {P} x {K_max} x {1 + S_max} x 3 x {B_max} values")
+    dev = [torch.as_tensor(a, device=xy.device) for a in (desc, r2, hull, cum)]
+    launched(model_lib().spadot_ripley_counts(_p(xy), _host(desc), _p(dev[0]), _host(r2), _p(dev[1]), _host(hull), _p(dev[2]),
+                                              _host(cum), _p(dev[3]), int(hull.shape[0]), P, K_max, S_max, B_max, _signed64(seed),
+                                              _p(out), _stream()), "spadot_ripley_counts", RIPLEY_LIMITS)
+    return out
+
+
+def ripley_counts(xy, desc, r2, windows, K_max, S_max, B_max, seed=0, out=None):
+    """The integers behind Ripley's L, G and F of every (problem, domain, pattern) in ONE counting launch (include/spadot_model.h:
+    spadot_ripley_counts).  xy: fp64 [sum n, 2] device tensor, per problem its spots ordered by (label, index), the problems back
+    to back; desc: int64 [P, 48] on the host as the header lays it out (columns 9 to 11, the place of the window, are filled in
+    here); r2[p]: the squared thresholds of problem p; windows[p]: its (vertices, cum) on the host.  Returns int64
+    [P, K_max, 1 + S_max, 3, B_max] (out: the tensor to write into).  ValueError, before any launch, outside the limits;
+    RuntimeError for a CPU tensor."""
+    return ripley_launch(xy, ripley_check(xy, desc, r2, windows, K_max, S_max, B_max), K_max, S_max, B_max, seed, out)
+
+
+def ripley_points(vertices, cum, seed, g, stream, count, device=None, out=None):
+    """The generated points 0 .. count - 1 of (seed, problem g, stream) in a window, by the device function that ripley_counts
+    uses (include/spadot_model.h: spadot_ripley_points).  vertices, cum: on the host.  Returns an fp64 device tensor [count, 2]
+    (out: the tensor to write into).  ValueError, before any launch, outside the limits; RuntimeError for a CPU tensor."""
+    need_cuda(out)
+    v, c = ripley_window(vertices, cum)
+    count, g, stream = int(count), int(g), int(stream)
+    if not 1 <= count <= RIPLEY_MAX_N:
+        raise ValueError(f"spadot_ripley_points writes 1 to {RIPLEY_MAX_N} points (got {count})")
+    if not 0 <= stream <= RIPLEY_MAX_STREAM or not 0 <= g <= RIPLEY_MAX_G:
+        raise ValueError(f"spadot_ripley_points takes a stream in 0 .. {RIPLEY_MAX_STREAM} and a problem number in 0 .. "
+                         f"{RIPLEY_MAX_G} (got stream {stream}, problem {g})")
+    if out is None:
+        dev = torch.device(device if device is not None else "cuda")
+        if dev.type != "cuda":
+            need_cuda(torch.empty(0))
+        out = torch.empty((count, 2), dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 2 * count:
+        raise ValueError(f"out must be a contiguous float64 tensor of {count} x 2 values")
+    with torch.cuda.device(out.device):
+        vd, cd = torch.as_tensor(v, device=out.device), torch.as_tensor(c, device=out.device)
+        launched(model_lib().spadot_ripley_points(_host(v), _p(vd), _host(c), _p(cd), int(v.shape[0]), _signed64(seed), g, stream,
+                                                  count, _p(out), _stream()), "spadot_ripley_points", RIPLEY_LIMITS)
+    return out

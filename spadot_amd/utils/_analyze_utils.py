@@ -230,6 +230,31 @@ def plot_cooccurrence(path, radii, ratio, timepoint, ring=False):
     fig.savefig(path)
 
 
+def plot_ripley(path, radii, observed, sim_mean, sim_min, sim_max, timepoint, pattern=None):
+    """{prefix}{tp}_ripley.png: one row per statistic (L, G, F), one panel per domain: the envelope of the simulations as a band,
+    their mean dashed, the observed curve on top; a statistic that is not defined leaves its panel empty."""
+    r = np.asarray(radii, dtype=np.float64)
+    obs = np.asarray(observed, dtype=np.float64)
+    K = obs.shape[1]
+    fig = _figure((2.6 * K + 0.8, 7.2))
+    for i, name in enumerate(("L", "G", "F")):
+        for c in range(K):
+            ax = fig.add_subplot(3, K, i * K + c + 1)
+            if not np.all(np.isnan(obs[i, c])):
+                ax.fill_between(r, np.asarray(sim_min)[i, c], np.asarray(sim_max)[i, c], color="0.8", linewidth=0)
+                ax.plot(r, np.asarray(sim_mean)[i, c], color="0.4", linewidth=0.8, linestyle="--")
+                ax.plot(r, obs[i, c], color="tab:red", linewidth=1.6)
+            if i == 0:
+                ax.set_title("domain {}{}".format(c, "" if pattern is None else "\n" + str(pattern[c])), fontsize=9)
+            if i == 2:
+                ax.set_xlabel("radius")
+            if c == 0:
+                ax.set_ylabel(name)
+    fig.suptitle("Ripley's L, G and F, time point: {}".format(timepoint))
+    fig.tight_layout(rect=(0, 0, 1, 0.96))
+    fig.savefig(path)
+
+
 def transition_min_prob(table):
     """Element-wise minimum of the column-normalised and the row-normalised transition table (_analyze_utils.py:184-194)."""
     t = np.asarray(table, dtype=np.float64)
