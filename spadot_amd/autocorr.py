@@ -30,12 +30,12 @@ Permutation null (P >= 1): mean and sd (ddof 0) of I_p and C_p give z_sim (NaN w
 
 The device sums; the host validates, takes the statistics and writes the files.  Limits: at most 2147483647 spots and edges per
 time point; permutation indices below 2^32."""
-import os
 import sys
 import time
 
 import numpy as np
 
+from .moran import centre_spread, columns, degenerate, moran_order, open_stage, refuse_edge_ends, timings
 from .utils._stage_utils import edge_pair, labeling_runs, savez_pinned
 
 FIELDS = ("I", "C", "z_norm_I", "p_norm_I", "z_sim_I", "p_sim_I", "padj_I", "z_norm_C", "p_norm_C", "z_sim_C", "p_sim_C",
@@ -84,8 +84,7 @@ def autocorr_stats(N, D, n, E, m2, moments, sumsq=None):
     G, P = N.shape[0], N.shape[1] - 1
     n, E = int(n), int(E)
     S0, S1, S2 = (float(v) for v in moments)
-    floor = np.zeros(G) if sumsq is None else n * 2.0 ** -50 * np.asarray(sumsq, dtype=np.float64)
-    bad = np.full(G, True) if n < 3 or E == 0 else ~(m2 > floor)
+    bad = degenerate(n, E, m2, sumsq)
     out = {"degenerate": bad}
     safe = np.where(bad, 1.0, m2)[:, None]
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -115,14 +114,6 @@ def autocorr_stats(N, D, n, E, m2, moments, sumsq=None):
                            (f"p_sim_{name}", p_sim), (f"padj_{name}", padj)):
                 out[key] = np.where(bad, np.nan, v)
     return out
-
-
-class _Csc:
-    """What autocorr_sums reads of a DeviceCounts, for data that is not one (the dense columns)."""
-
-    def __init__(self, colptr, ridx, tp_off_host, G, device):
-        self.colptr, self.ridx, self.tp_off_host, self.G, self.device = colptr, ridx, tp_off_host, int(G), device
-        self.T, self.n = len(tp_off_host) - 1, int(tp_off_host[-1])
 
 
 def _gene_range(genes, G):
@@ -160,12 +151,7 @@ def autocorr_sums(edges, dc, values, centre, n_perms, seed=0, first=0, observed=
         raise ValueError(f"the number of permutations must not be negative (got n_perms = {n_perms})")
     off = np.asarray(dc.tp_off_host, dtype=np.int64)
     with torch.cuda.device(dc.device):
-        wide = [(t, torch.stack(torch.aminmax(torch.cat([s.reshape(-1), d.reshape(-1)]))).long()) for t, (s, d) in enumerate(pairs)
-                if s.dtype != torch.int32 and s.numel()]
-        if wide:                                             # the range is taken before the ends are narrowed to int32
-            for (t, _), (lo, hi) in zip(wide, torch.stack([w for _, w in wide]).cpu().tolist()):
-                if lo < 0 or hi >= off[t + 1] - off[t]:
-                    raise ValueError(f"time point {t} has edge ends {lo} .. {hi}: they must lie in 0 .. {int(off[t + 1] - off[t]) - 1}")
+        refuse_edge_ends(pairs, np.diff(off), wide_only=True)
         eoff = np.concatenate([[0], np.cumsum([int(s.shape[0]) for s, _ in pairs])]).astype(np.int64)
         src = torch.cat([s.to(torch.int32) for s, _ in pairs]) if T > 1 else pairs[0][0].to(torch.int32).contiguous()
         dst = torch.cat([d.to(torch.int32) for _, d in pairs]) if T > 1 else pairs[0][1].to(torch.int32).contiguous()
@@ -190,49 +176,6 @@ def autocorr_sums(edges, dc, values, centre, n_perms, seed=0, first=0, observed=
     return [N[t] for t in range(T)], [D[t] for t in range(T)]
 
 
-def _dense_csc(dense, device):
-    """Per-graph dense [n, C] device tensors as one CSC with every entry stored: (a _Csc, its fp32 values)."""
-    import torch
-    if not dense or any(not isinstance(x, torch.Tensor) for x in dense):
-        raise RuntimeError("spatial_autocorr takes a DeviceCounts or one dense device tensor [n, C] per time point")
-    C = None
-    for t, x in enumerate(dense):
-        if not x.is_cuda:
-            raise RuntimeError("spadot_amd takes the autocorrelation on the MI355X only (got a CPU tensor); there is no CPU path")
-        if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1 or x.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"the columns of time point {t} must be a float32 or float64 tensor [n, C] (got {tuple(x.shape)} "
-                             f"{x.dtype})")
-        if C is not None and int(x.shape[1]) != C:
-            raise ValueError(f"every time point must hold the same {C} columns (time point {t}: {int(x.shape[1])})")
-        C = int(x.shape[1])
-    off = np.concatenate([[0], np.cumsum([int(x.shape[0]) for x in dense])]).astype(np.int64)
-    n = int(off[-1])
-    if n * C > 2 ** 31 - 1:
-        raise ValueError(f"{n} spots x {C} columns: the dense path stores every entry and takes at most {2 ** 31 - 1}")
-    X = torch.cat([x.to(device=device, dtype=torch.float32) for x in dense])                   # [n, C]
-    if not bool(torch.isfinite(X).all()):
-        raise ValueError("the dense columns hold entries that are not finite")
-    colptr = torch.arange(C + 1, dtype=torch.int64, device=device) * n
-    ridx = torch.arange(n, dtype=torch.int32, device=device).repeat(C)
-    return _Csc(colptr, ridx, off, C, device), X.t().contiguous().reshape(-1)
-
-
-def _moments(dc, values):
-    """Per (time point, gene): the stored count, sum v and sum v^2 in fp64, a fixed order (trends.weighted_moments with a
-    column of ones for a DeviceCounts)."""
-    import torch
-    if isinstance(dc, _Csc):                                 # every entry stored: the columns are rows of a [C, n] matrix
-        V = values.reshape(dc.G, dc.n).to(torch.float64)
-        off = dc.tp_off_host
-        S1 = torch.stack([V[:, int(off[t]):int(off[t + 1])].sum(1) for t in range(dc.T)])
-        S2 = torch.stack([(V[:, int(off[t]):int(off[t + 1])] ** 2).sum(1) for t in range(dc.T)])
-        S0 = torch.as_tensor(np.diff(off).astype(np.float64), device=dc.device)[:, None].expand(dc.T, dc.G)
-        return S0, S1, S2
-    from .trends import weighted_moments
-    S0, S1, S2 = weighted_moments(dc, values, torch.ones((dc.n, 1), dtype=torch.float64, device=dc.device))
-    return S0[:, :, 0], S1[:, :, 0], S2[:, :, 0]
-
-
 def spatial_autocorr(edges, data, values=None, n_perms=100, seed=0, lds_limit=None):
     """Moran's I and Geary's C of every gene of every time point with both nulls (module docstring).  edges[t]: (src, dst) device
     tensors of time point t (spatial_edges); data: a DeviceCounts (values: its fp32 values in CSC order, default
@@ -244,25 +187,14 @@ def spatial_autocorr(edges, data, values=None, n_perms=100, seed=0, lds_limit=No
     n_perms = int(n_perms)
     if n_perms < 0:
         raise ValueError(f"the number of permutations must not be negative (got n_perms = {n_perms})")
-    if hasattr(data, "colptr"):
-        dc = data
-        if values is None:
-            from .trends import lognorm_values
-            values = lognorm_values(dc)
-    else:
-        if values is not None:
-            raise ValueError("values go with a DeviceCounts; dense columns are their own values")
-        dev = data[0].device if data and isinstance(data[0], torch.Tensor) else None
-        dc, values = _dense_csc(data, dev)
-    with torch.cuda.device(dc.device):
-        S0, S1, S2 = _moments(dc, values)
-        n_t = torch.as_tensor(np.diff(np.asarray(dc.tp_off_host)).astype(np.float64), device=dc.device)[:, None]
-        centre = (S1 / n_t).contiguous()
-        m2 = torch.clamp(S2 - S1 * S1 / n_t, min=0.0)
-        N, D = autocorr_sums(edges, dc, values, centre, n_perms, seed=seed, lds_limit=lds_limit)
-        moments = [graph_moments(s, d, int(n_t[t, 0].item())) for t, (s, d) in enumerate(edges)]
-        centre, m2, S2, pct = centre.cpu().numpy(), m2.cpu().numpy(), S2.cpu().numpy(), (S0 / n_t).cpu().numpy()
+    dc = columns(data, values)
     off = np.asarray(dc.tp_off_host, dtype=np.int64)
+    with torch.cuda.device(dc.device):
+        S0, centre, m2, S2 = centre_spread(dc)
+        N, D = autocorr_sums(edges, dc, dc.values, centre, n_perms, seed=seed, lds_limit=lds_limit)
+        moments = [graph_moments(s, d, int(off[t + 1] - off[t])) for t, (s, d) in enumerate(edges)]
+        n_t = torch.as_tensor(np.diff(off).astype(np.float64), device=dc.device)[:, None]
+        centre, m2, S2, pct = centre.cpu().numpy(), m2.cpu().numpy(), S2.cpu().numpy(), (S0 / n_t).cpu().numpy()
     return [AutocorrResult(N[t], D[t], int(off[t + 1] - off[t]), moments[t][0], centre[t], m2[t], S2[t], pct[t], moments[t])
             for t in range(dc.T)]
 
@@ -270,8 +202,7 @@ def spatial_autocorr(edges, data, values=None, n_perms=100, seed=0, lds_limit=No
 def autocorr_table(r, genes, top=100):
     """The rows of {prefix}autocorr_{tp}.csv: the `top` genes (0 = all) by I descending (NaN last), then gene column."""
     import pandas as pd
-    G = r.I.shape[0]
-    order = np.lexsort((np.arange(G), -np.where(np.isnan(r.I), -np.inf, r.I)))
+    order = moran_order(r.I)
     if top:
         order = order[:top]
     cols = {"gene": np.asarray(genes)[order]}
@@ -286,9 +217,6 @@ def autocorr(args):
     genes, k, n_perms, seed; pinned time stamps: two runs with one seed write the same bytes).  Returns {'tables', 'results' (per
     time point), 'timepoints', 'timings'}."""
     import torch
-    from .markers import load_marker_counts
-    from .neighbors import spatial_edges
-    from .preprocess import DeviceCounts
     from .trends import lognorm_values
     t_start = time.perf_counter()
     top = getattr(args, "top", 100)
@@ -297,42 +225,24 @@ def autocorr(args):
     if top < 0 or k < 1 or n_perms < 0:
         raise ValueError(f"the autocorr stage takes top >= 0, k >= 1 and n_perms >= 0 (got top = {top}, k = {k}, n_perms = "
                          f"{n_perms})")
-    device = getattr(args, "device", None) or "cuda:0"
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("spadot_amd takes the autocorrelation on the MI355X only (device 'cuda:N'); there is no CPU path")
-    raw, path = load_marker_counts(args.data)
-    if not getattr(args, "output_dir", None):
-        args.output_dir = os.path.dirname(path) if path else os.getcwd()
-    os.makedirs(args.output_dir, exist_ok=True)
-    prefix = getattr(args, "prefix", "") or ""
-    dc = DeviceCounts(raw, dev)
-    if not np.all(np.isfinite(dc.spatial)):
-        raise ValueError("the data holds spots without finite spatial coordinates")
-    tps = [str(t) for t in dc.tps]
-    off = dc.tp_off_host
-    t_read = time.perf_counter()
-    edges = [spatial_edges(dc.spatial[int(off[t]):int(off[t + 1])], k, dev) for t in range(dc.T)]
-    torch.cuda.synchronize(dev)
-    t_graph = time.perf_counter()
-    with torch.cuda.device(dev):
-        res = spatial_autocorr(edges, dc, lognorm_values(dc), n_perms=n_perms, seed=seed)
-    torch.cuda.synchronize(dev)
+    st = open_stage(args, k, "the autocorrelation", t_start)
+    dc, tps = st.dc, st.tps
+    with torch.cuda.device(st.dev):
+        res = spatial_autocorr(st.edges, dc, lognorm_values(dc), n_perms=n_perms, seed=seed)
+    torch.cuda.synchronize(st.dev)
     t_dev = time.perf_counter()
     tables = {}
     arrays = dict(timepoints=np.asarray(tps), genes=np.asarray(dc.genes).astype(str), k=np.int64(k), n_perms=np.int64(n_perms),
                   seed=np.int64(seed))
     for tp, r in zip(tps, res):
         tables[tp] = autocorr_table(r, dc.genes, top)
-        tables[tp].to_csv(os.path.join(args.output_dir, f"{prefix}autocorr_{tp}.csv"), index=False)
+        tables[tp].to_csv(st.path(f"autocorr_{tp}.csv"), index=False)
         for name in ARRAYS:
             arrays[f"{tp}_{name}"] = getattr(r, name)
         for name in ("S0", "S1", "S2"):
             arrays[f"{tp}_{name}"] = np.int64(getattr(r, name))
-    savez_pinned(os.path.join(args.output_dir, prefix + "autocorr.npz"), arrays)
+    savez_pinned(st.path("autocorr.npz"), arrays)
     t_end = time.perf_counter()
     print(f"autocorr: {dc.G} genes x {dc.n} spots of {dc.T} time points, k = {k}, {n_perms} permutations, written to "
           f"{args.output_dir}", file=sys.stderr)
-    return {"tables": tables, "results": dict(zip(tps, res)), "timepoints": tps,
-            "timings": dict(read_s=t_read - t_start, graph_s=t_graph - t_read, device_s=t_dev - t_graph, write_s=t_end - t_dev,
-                            total_s=t_end - t_start)}
+    return {"tables": tables, "results": dict(zip(tps, res)), "timepoints": tps, "timings": timings(st, t_dev, t_end)}

@@ -20,7 +20,7 @@
 
 #include "../../include/spadot_model.h"
 #include "per_device.h"
-#include "feistel_perm.h"
+#include "csc_image.h"
 
 #define AC_DESC 7                  // int64 columns of a time point's descriptor (include/spadot_model.h)
 #define AC_LDS_BYTES 163840        // one workgroup may take the whole LDS of a compute unit
@@ -50,35 +50,12 @@ __device__ __forceinline__ void ac_pass(float *__restrict__ img, const AcItem &a
     const unsigned tid = threadIdx.x;
     if (tid < 2 * GS) {                                  // the rows of this time point in the gene's column: two lower bounds
         const int k = tid >> 1;
-        long long lo = 0, hi = 0;
-        if (k < a.genes) {
-            lo = a.colptr[a.gene0 + k];
-            hi = a.colptr[a.gene0 + k + 1];
-            lo = lo < 0 ? 0 : (lo > a.nnz ? a.nnz : lo);
-            hi = hi < lo ? lo : (hi > a.nnz ? a.nnz : hi);
-            const long long want = a.row0 + ((tid & 1) ? (long long)a.n : 0LL);
-            while (lo < hi) {
-                const long long mid = lo + ((hi - lo) >> 1);
-                if ((long long)a.ridx[mid] < want) lo = mid + 1; else hi = mid;
-            }
-        }
-        seg[tid] = lo;
+        seg[tid] = k < a.genes ? csc_lower_bound(a.ridx, a.colptr[a.gene0 + k], a.colptr[a.gene0 + k + 1], a.nnz,
+                                                 a.row0 + ((tid & 1) ? (long long)a.n : 0LL)) : 0LL;
     }
-    const unsigned long long total = (unsigned long long)a.n * GS, quads = total >> 2;
-    for (unsigned long long i = tid; i < quads; i += THREADS) reinterpret_cast<float4 *>(img)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (unsigned long long i = (quads << 2) + tid; i < total; i += THREADS) img[i] = 0.f;
+    csc_image_zero<THREADS, GS>(img, a.n);
     __syncthreads();
-#pragma unroll
-    for (int k = 0; k < GS; ++k) {
-        const long long hi = seg[2 * k + 1];
-        for (long long idx = seg[2 * k] + tid; idx < hi; idx += THREADS) {
-            const long long r = (long long)a.ridx[idx] - a.row0;
-            if (r >= 0 && r < (long long)a.n) {          // true between the two bounds of a sorted column; kept as the guard
-                const unsigned i = a.perm ? ac_perm_inv(q, (unsigned)r) : (unsigned)r;
-                img[(unsigned long long)i * GS + k] = a.vals[idx];
-            }
-        }
-    }
+    csc_image_scatter<THREADS, GS>(img, seg, a.ridx, a.vals, a.row0, a.n, a.perm, q);
     __syncthreads();
 #pragma unroll
     for (int v = 0; v < 2 * GS; ++v) acc[v] = 0.0;

@@ -27,7 +27,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/spadot_model.h"
-#include "feistel_perm.h"
+#include "csc_image.h"
 
 #define CM_DESC 9                  // int64 columns of a time point's descriptor (include/spadot_model.h)
 #define CM_THREADS 256             // four wavefronts: 2 x 2 quarters of a tile
@@ -66,8 +66,7 @@ __global__ void __launch_bounds__(256) k_cross_fill(const double *__restrict__ c
     if (idx >= a.npad * GP) return;
     const long long i = idx / GP;
     const int j = (int)(idx - i * GP);
-    int g = genes[j < ng ? j : 0];                       // a selected gene out of range is refused on the host
-    g = g < 0 ? 0 : (g >= G ? G - 1 : g);
+    const int g = csc_gene(genes[j < ng ? j : 0], G);
     const double c = centre[(long long)t * G + g];
     Z[(a.zoff + i) * GP + j] = (i < a.n && j < ng) ? 0.0 - c : 0.0;
 }
@@ -81,19 +80,9 @@ __global__ void __launch_bounds__(256) k_cross_scatter(const long long *__restri
     const int j = blockIdx.x, t = blockIdx.y;
     const CmTp a = cm_tp(desc, t, zrows);
     if (!a.ok) return;
-    int g = genes[j];
-    g = g < 0 ? 0 : (g >= G ? G - 1 : g);
-    if (threadIdx.x < 2) {                               // the rows of this time point in the gene's column: two lower bounds
-        long long lo = colptr[g], hi = colptr[g + 1];
-        lo = lo < 0 ? 0 : (lo > nnz ? nnz : lo);
-        hi = hi < lo ? lo : (hi > nnz ? nnz : hi);
-        const long long want = a.row0 + (threadIdx.x ? a.n : 0LL);
-        while (lo < hi) {
-            const long long mid = lo + ((hi - lo) >> 1);
-            if ((long long)ridx[mid] < want) lo = mid + 1; else hi = mid;
-        }
-        seg[threadIdx.x] = lo;
-    }
+    const int g = csc_gene(genes[j], G);
+    if (threadIdx.x < 2)                                 // the rows of this time point in the gene's column: two lower bounds
+        seg[threadIdx.x] = csc_lower_bound(ridx, colptr[g], colptr[g + 1], nnz, a.row0 + (threadIdx.x ? a.n : 0LL));
     __syncthreads();
     const double c = centre[(long long)t * G + g];
     const long long hi = seg[1];
@@ -115,13 +104,10 @@ __global__ void __launch_bounds__(256) k_cross_lag(const int *__restrict__ rowpt
     const int j = (int)(idx - i * GP);
     double acc = 0.0;
     if (i < a.n) {
-        // a rowptr that does not ascend from 0 to E is refused on the host before the launch; the clamps keep every access
-        // inside col, and a neighbour out of range (refused on the host as well) reads spot 0 and is not added
-        const int *rp = rowptr + a.roff;
+        // a neighbour out of range (refused on the host as the rowptr is) reads spot 0 and is not added
         const int *cl = col + a.eoff;
-        long long r0 = rp[i], r1 = rp[i + 1];
-        r0 = r0 < 0 ? 0 : (r0 > a.E ? a.E : r0);
-        r1 = r1 < r0 ? r0 : (r1 > a.E ? a.E : r1);
+        long long r0, r1;
+        csr_row(rowptr + a.roff, i, a.E, r0, r1);
         for (long long e = r0; e < r1; ++e) {
             const long long nb = cl[e];
             const bool ok = nb >= 0 && nb < a.n;

@@ -1,6 +1,6 @@
-// feistel_perm.h -- the permutation pi_p of (seed, graph id, p, n) that the neighbors, autocorr, ligrec and hotspots stages share (restated
-// in numpy in tests/nhood_ref.py): a six-round balanced Feistel network with cycle walking, evaluated per element; no permutation
-// is stored or sorted anywhere.
+// feistel_perm.h -- the permutation pi_p of (seed, graph id, p, n) that the neighbors, autocorr, ligrec, hotspots, modules and
+// ripley stages share (restated in numpy in tests/nhood_ref.py): a six-round balanced Feistel network with cycle
+// walking, evaluated per element; no permutation is stored or sorted anywhere.
 #ifndef SPADOT_FEISTEL_PERM_H
 #define SPADOT_FEISTEL_PERM_H
 #include <hip/hip_runtime.h>

@@ -27,7 +27,7 @@
 
 #include "../../include/spadot_model.h"
 #include "per_device.h"
-#include "feistel_perm.h"
+#include "csc_image.h"
 
 #define LM_DESC 8                  // int64 columns of a time point's descriptor (include/spadot_model.h)
 #define LM_LDS_BYTES 163840        // one workgroup may take the whole LDS of a compute unit
@@ -55,33 +55,18 @@ __device__ __forceinline__ void lm_pass(float *__restrict__ img, const LmItem &a
                                         LmLag<GS> *__restrict__ lag0, LmCnt<GS> *__restrict__ cnt, unsigned long long seed,
                                         unsigned long long gid, unsigned long long p0, int np) {
     const unsigned tid = threadIdx.x;
-    const unsigned long long total = (unsigned long long)a.n * GS, quads = total >> 2;
     for (int l = 0; l <= np; ++l) {                      // labeling 0 is the identity, 1 + u permutation p0 + u
         const bool perm = l > 0;
         NhPerm q = {};
         if (perm) q = nh_perm_setup(seed, gid, p0 + (unsigned long long)(l - 1), a.n);
         __syncthreads();                                 // the bounds are written; the image of the labeling before is read
-        for (unsigned long long i = tid; i < quads; i += THREADS) reinterpret_cast<float4 *>(img)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (unsigned long long i = (quads << 2) + tid; i < total; i += THREADS) img[i] = 0.f;
+        csc_image_zero<THREADS, GS>(img, a.n);
         __syncthreads();
-#pragma unroll
-        for (int k = 0; k < GS; ++k) {
-            const long long hi = seg[2 * k + 1];
-            for (long long idx = seg[2 * k] + tid; idx < hi; idx += THREADS) {
-                const long long r = (long long)a.ridx[idx] - a.row0;
-                if (r >= 0 && r < (long long)a.n) {      // true between the two bounds of a sorted column; kept as the guard
-                    const unsigned i = perm ? ac_perm_inv(q, (unsigned)r) : (unsigned)r;
-                    img[(unsigned long long)i * GS + k] = a.vals[idx];
-                }
-            }
-        }
+        csc_image_scatter<THREADS, GS>(img, seg, a.ridx, a.vals, a.row0, a.n, perm, q);
         __syncthreads();
         for (unsigned i = tid; i < a.n; i += THREADS) {
-            // a rowptr that does not ascend from 0 to E is refused on the host before the launch; the clamps keep every
-            // access inside col
-            long long r0 = a.rowptr[i], r1 = a.rowptr[i + 1];
-            r0 = r0 < 0 ? 0 : (r0 > (long long)a.E ? (long long)a.E : r0);
-            r1 = r1 < r0 ? r0 : (r1 > (long long)a.E ? (long long)a.E : r1);
+            long long r0, r1;
+            csr_row(a.rowptr, i, a.E, r0, r1);
             const unsigned jstar = perm ? ac_perm_inv(q, i) : i;
             double acc[GS];
 #pragma unroll
@@ -148,25 +133,15 @@ __global__ void __launch_bounds__(THREADS) k_local_lag(const int *__restrict__ r
     double cg[GS];
 #pragma unroll
     for (int k = 0; k < GS; ++k) {
-        int g = genes[k < a.genes ? grp * GS + k : grp * GS];    // a selected gene out of range is refused on the host
-        g = g < 0 ? 0 : (g >= G ? G - 1 : g);
+        const int g = csc_gene(genes[k < a.genes ? grp * GS + k : grp * GS], G);
         cg[k] = k < a.genes ? centre[(long long)t * G + g] : 0.0;
     }
     if (tid < 2 * GS) {                                  // the rows of this time point in the gene's column: two lower bounds
         const int k = tid >> 1;
-        long long lo = 0, hi = 0;
+        long long lo = 0;
         if (k < a.genes) {
-            int g = genes[grp * GS + k];
-            g = g < 0 ? 0 : (g >= G ? G - 1 : g);
-            lo = colptr[g];
-            hi = colptr[g + 1];
-            lo = lo < 0 ? 0 : (lo > nnz ? nnz : lo);
-            hi = hi < lo ? lo : (hi > nnz ? nnz : hi);
-            const long long want = a.row0 + ((tid & 1) ? (long long)a.n : 0LL);
-            while (lo < hi) {
-                const long long mid = lo + ((hi - lo) >> 1);
-                if ((long long)ridx[mid] < want) lo = mid + 1; else hi = mid;
-            }
+            const int g = csc_gene(genes[grp * GS + k], G);
+            lo = csc_lower_bound(ridx, colptr[g], colptr[g + 1], nnz, a.row0 + ((tid & 1) ? (long long)a.n : 0LL));
         }
         seg[tid] = lo;
     }

@@ -30,12 +30,13 @@ without out-edges has lag 0, I 0, quadrant 0 and NaN in p_sim and padj; a gene t
 3, E = 0 or m2 <= n 2^-50 sum v^2) is NaN throughout with quadrant 0.  Out of scope: Getis-Ord G_i*, row-standardised weights.
 
 Limits: at most 2147483647 spots and edges per time point; permutation indices below 2^32."""
-import os
 import sys
 import time
 
 import numpy as np
 
+from .moran import centre_spread, columns, degenerate, edge_csr, gene_selection, open_stage, timings, top_genes
+from .moran import read_genes  # noqa: F401  (the --genes of this stage: callers import it from here)
 from .utils._stage_utils import edge_pair, savez_pinned
 
 FIELDS = ("I", "quadrant", "p_sim", "padj", "lag", "ge", "le")
@@ -92,42 +93,6 @@ def local_stats(lag, ge, le, z, m2, n, P, has_neighbours, degenerate):
     return {"I": I, "quadrant": quadrant, "p_sim": p_sim, "padj": padj, "larger": larger, "smaller": smaller}
 
 
-def _selection(genes, G):
-    sel = np.asarray(genes).reshape(-1)
-    if sel.size < 1 or sel.dtype.kind not in "iu":
-        raise ValueError("genes must be a selection of at least one integer gene index (repeats and any order are taken)")
-    if sel.min() < 0 or sel.max() >= G:
-        raise ValueError(f"the selected genes {int(sel.min())} .. {int(sel.max())} must lie in 0 .. {G - 1}")
-    return sel.astype(np.int32)
-
-
-def _csr(pairs, sizes, device):
-    """The CSR of every time point on the device: the edges sorted stably by source.  Refuses edge ends outside 0 .. n-1 first
-    (one host round trip).  Returns (rowptr int32 [sum (n + 1)], col int32 [sum E], the descriptor [T, 8])."""
-    import torch
-    from . import stage_ops as ops
-    some = [(t, torch.stack(torch.aminmax(torch.cat([s.reshape(-1), d.reshape(-1)]))).long()) for t, (s, d) in enumerate(pairs)
-            if s.numel()]
-    if some:                                                 # the range is taken before the ends are sorted and narrowed
-        for (t, _), (lo, hi) in zip(some, torch.stack([w for _, w in some]).cpu().tolist()):
-            if lo < 0 or hi >= sizes[t]:
-                raise ValueError(f"time point {t} has edge ends {lo} .. {hi}: they must lie in 0 .. {int(sizes[t]) - 1}")
-    rowptrs, cols = [], []
-    desc = np.zeros((len(pairs), ops.LOCAL_DESC), dtype=np.int64)
-    eoff = roff = row0 = 0
-    for t, (s, d) in enumerate(pairs):
-        n, E = int(sizes[t]), int(s.numel())
-        s = s.reshape(-1).long()
-        order = torch.sort(s, stable=True).indices
-        cols.append(d.reshape(-1)[order].to(torch.int32))
-        rp = torch.zeros(n + 1, dtype=torch.int64, device=device)
-        rp[1:] = torch.cumsum(torch.bincount(s, minlength=n), 0)
-        rowptrs.append(rp.to(torch.int32))
-        desc[t, :6] = (eoff, n, E, row0, t, roff)
-        eoff, roff, row0 = eoff + E, roff + n + 1, row0 + n
-    return torch.cat(rowptrs).contiguous(), torch.cat(cols).contiguous(), desc
-
-
 def local_lag(edges, dc, values, centre, genes, n_perms, seed=0, first=0, lds_limit=None, threads=None, gs=None, perm_chunk=None):
     """lag, ge and le of every (selected gene, spot) of every time point (module docstring).  edges[t]: (src, dst) integer device
     tensors of time point t, in the order of dc's time points (any edge order: the rows are built here by a stable sort by
@@ -148,13 +113,13 @@ def local_lag(edges, dc, values, centre, genes, n_perms, seed=0, first=0, lds_li
     if not isinstance(values, torch.Tensor):
         raise RuntimeError("local_lag takes the values as a device tensor (torch), not a host array")
     centre = centre if isinstance(centre, torch.Tensor) else torch.as_tensor(np.asarray(centre, dtype=np.float64), device=dc.device)
-    sel = _selection(genes, G)
+    sel = gene_selection(genes, G)
     n_perms, first = int(n_perms), int(first)
     if n_perms < 1:
         raise ValueError(f"local_lag takes at least one permutation (got n_perms = {n_perms})")
     off = np.asarray(dc.tp_off_host, dtype=np.int64)
     with torch.cuda.device(dc.device):
-        rowptr, col, desc = _csr(pairs, np.diff(off), dc.device)
+        rowptr, col, desc = edge_csr(pairs, np.diff(off), dc.device)
         desc[:, 3] = off[:-1]
         gsel = torch.as_tensor(sel, device=dc.device)
         args = (rowptr, col, dc.colptr, dc.ridx, values, centre.contiguous(), gsel)
@@ -192,56 +157,26 @@ def local_moran(edges, data, genes, values=None, n_perms=999, seed=0, lds_limit=
     memberships, taken as fp32; genes: gene (column) indices.  Time point t permutes under (seed, t).  Returns [t] ->
     HotspotResult."""
     import torch
-    from .autocorr import _dense_csc, _moments
     n_perms = int(n_perms)
     if n_perms < 1:
         raise ValueError(f"local Moran's I takes at least one permutation (got n_perms = {n_perms})")
-    if hasattr(data, "colptr"):
-        dc = data
-        if values is None:
-            from .trends import lognorm_values
-            values = lognorm_values(dc)
-    else:
-        if values is not None:
-            raise ValueError("values go with a DeviceCounts; dense columns are their own values")
-        dev = data[0].device if data and isinstance(data[0], torch.Tensor) else None
-        dc, values = _dense_csc(data, dev)
-    sel = _selection(genes, int(dc.G))
+    dc = columns(data, values)
+    sel = gene_selection(genes, dc.G)
     off = np.asarray(dc.tp_off_host, dtype=np.int64)
     with torch.cuda.device(dc.device):
-        _, S1, S2 = _moments(dc, values)
-        n_t = torch.as_tensor(np.diff(off).astype(np.float64), device=dc.device)[:, None]
-        centre = (S1 / n_t).contiguous()
-        m2 = torch.clamp(S2 - S1 * S1 / n_t, min=0.0)
-        parts = local_lag(edges, dc, values, centre, sel, n_perms, seed=seed, lds_limit=lds_limit)
-        dense = _dense_rows(dc, values, sel).to(torch.float64).cpu().numpy()
+        _, centre, m2, S2 = centre_spread(dc)
+        parts = local_lag(edges, dc, dc.values, centre, sel, n_perms, seed=seed, lds_limit=lds_limit)
+        dense = _dense_rows(dc, dc.values, sel).to(torch.float64).cpu().numpy()
         outdeg = [torch.bincount(edge_pair(e, dc.device, t)[0].reshape(-1).long(), minlength=int(off[t + 1] - off[t])).cpu().numpy()
                   for t, e in enumerate(edges)]
         centre, m2, S2 = centre.cpu().numpy()[:, sel], m2.cpu().numpy()[:, sel], S2.cpu().numpy()[:, sel]
     res = []
     for t in range(dc.T):
         n, E = int(off[t + 1] - off[t]), int(outdeg[t].sum())
-        bad = np.full(sel.size, True) if n < 3 or E == 0 else ~(m2[t] > n * 2.0 ** -50 * S2[t])
         z = dense[:, off[t]:off[t + 1]] - centre[t][:, None]
-        res.append(HotspotResult(*parts[t], z, centre[t], m2[t], n, E, n_perms, outdeg[t] > 0, bad, sel))
+        res.append(HotspotResult(*parts[t], z, centre[t], m2[t], n, E, n_perms, outdeg[t] > 0,
+                                 degenerate(n, E, m2[t], S2[t]), sel))
     return res
-
-
-def read_genes(spec, names):
-    """The gene indices of --genes: a comma list of names, or a file with one name per line.  Unknown names: ValueError."""
-    names = np.asarray(names).astype(str)
-    if os.path.exists(spec):
-        with open(spec) as f:
-            want = [line.strip() for line in f if line.strip()]
-    else:
-        want = [w.strip() for w in str(spec).split(",") if w.strip()]
-    if not want:
-        raise ValueError(f"--genes names no gene ({spec!r})")
-    where = {g: i for i, g in reversed(list(enumerate(names.tolist())))}
-    unknown = [w for w in want if w not in where]
-    if unknown:
-        raise ValueError(f"--genes names {len(unknown)} genes that the data does not hold: {', '.join(unknown[:10])}")
-    return np.asarray([where[w] for w in want], dtype=np.int32)
 
 
 def significant(r, alpha=0.05, fdr=False):
@@ -290,9 +225,7 @@ def hotspots(args):
     'domain_tables', 'results' (per time point), 'genes', 'timepoints', 'timings'}."""
     import torch
     from .autocorr import spatial_autocorr
-    from .markers import load_marker_counts, read_domains
-    from .neighbors import spatial_edges
-    from .preprocess import DeviceCounts
+    from .markers import read_domains
     from .trends import lognorm_values
     t_start = time.perf_counter()
     top = getattr(args, "top", 50)
@@ -303,56 +236,34 @@ def hotspots(args):
     if top < 1 or k < 1 or n_perms < 1 or not 0.0 < alpha <= 1.0:
         raise ValueError(f"the hotspots stage takes top >= 1, k >= 1, n_perms >= 1 and 0 < alpha <= 1 (got top = {top}, k = {k}, "
                          f"n_perms = {n_perms}, alpha = {alpha})")
-    device = getattr(args, "device", None) or "cuda:0"
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("spadot_amd takes the local autocorrelation on the MI355X only (device 'cuda:N'); there is no CPU path")
-    raw, path = load_marker_counts(args.data)
-    sel = read_genes(args.genes, raw.var_names) if getattr(args, "genes", None) else None
-    labels = read_domains(args.domains, raw.obs["timepoint"]) if getattr(args, "domains", None) else None
-    if not getattr(args, "output_dir", None):
-        args.output_dir = os.path.dirname(path) if path else os.getcwd()
-    os.makedirs(args.output_dir, exist_ok=True)
-    prefix = getattr(args, "prefix", "") or ""
-    dc = DeviceCounts(raw, dev)
-    if not np.all(np.isfinite(dc.spatial)):
-        raise ValueError("the data holds spots without finite spatial coordinates")
-    tps = [str(t) for t in dc.tps]
-    off = dc.tp_off_host
-    t_read = time.perf_counter()
-    edges = [spatial_edges(dc.spatial[int(off[t]):int(off[t + 1])], k, dev) for t in range(dc.T)]
-    torch.cuda.synchronize(dev)
-    t_graph = time.perf_counter()
-    with torch.cuda.device(dev):
+    st = open_stage(args, k, "the local autocorrelation", t_start, lambda raw: (
+        read_genes(args.genes, raw.var_names) if getattr(args, "genes", None) else None,
+        read_domains(args.domains, raw.obs["timepoint"]) if getattr(args, "domains", None) else None))
+    (sel, labels), dc, tps = st.extras, st.dc, st.tps
+    with torch.cuda.device(st.dev):
         values = lognorm_values(dc)
         if sel is None:                                      # the top genes by Moran's I of every time point, unioned
-            glob = spatial_autocorr(edges, dc, values, n_perms=0)
-            picked = set()
-            for r in glob:
-                order = np.lexsort((np.arange(dc.G), -np.where(np.isnan(r.I), -np.inf, r.I)))
-                picked.update(int(g) for g in order[:top] if not np.isnan(r.I[g]))
-            if not picked:
+            sel = top_genes(spatial_autocorr(st.edges, dc, values, n_perms=0), top)
+            if not sel.size:
                 raise ValueError("no gene has a Moran's I in any time point: nothing to test")
-            sel = np.asarray(sorted(picked), dtype=np.int32)
-        res = local_moran(edges, dc, sel, values, n_perms=n_perms, seed=seed)
-    torch.cuda.synchronize(dev)
+        res = local_moran(st.edges, dc, sel, values, n_perms=n_perms, seed=seed)
+    torch.cuda.synchronize(st.dev)
     t_dev = time.perf_counter()
     tables, domain_tables = {}, {}
     arrays = dict(timepoints=np.asarray(tps), genes=np.asarray(dc.genes).astype(str)[sel], k=np.int64(k), n_perms=np.int64(n_perms),
                   seed=np.int64(seed), alpha=np.float64(alpha))
     for t, (tp, r) in enumerate(zip(tps, res)):
         tables[tp] = hotspot_table(r, dc.genes, alpha, fdr)
-        tables[tp].to_csv(os.path.join(args.output_dir, f"{prefix}hotspots_{tp}.csv"), index=False)
+        tables[tp].to_csv(st.path(f"hotspots_{tp}.csv"), index=False)
         for name in FIELDS:
             arrays[f"{tp}_{name}"] = getattr(r, name)
-        arrays[f"{tp}_spots"] = np.asarray(dc.perm[int(off[t]):int(off[t + 1])], dtype=np.int64)
+        arrays[f"{tp}_spots"] = np.asarray(dc.perm[st.rows(t)], dtype=np.int64)
         if labels is not None:
-            domain_tables[tp] = domain_table(r, dc.genes, labels[dc.perm[int(off[t]):int(off[t + 1])]], alpha, fdr)
-            domain_tables[tp].to_csv(os.path.join(args.output_dir, f"{prefix}hotspots_domains_{tp}.csv"), index=False)
-    savez_pinned(os.path.join(args.output_dir, prefix + "hotspots.npz"), arrays)
+            domain_tables[tp] = domain_table(r, dc.genes, labels[dc.perm[st.rows(t)]], alpha, fdr)
+            domain_tables[tp].to_csv(st.path(f"hotspots_domains_{tp}.csv"), index=False)
+    savez_pinned(st.path("hotspots.npz"), arrays)
     t_end = time.perf_counter()
     print(f"hotspots: {sel.size} genes x {dc.n} spots of {dc.T} time points, k = {k}, {n_perms} permutations, written to "
           f"{args.output_dir}", file=sys.stderr)
     return {"tables": tables, "domain_tables": domain_tables, "results": dict(zip(tps, res)), "genes": sel, "timepoints": tps,
-            "timings": dict(read_s=t_read - t_start, graph_s=t_graph - t_read, device_s=t_dev - t_graph, write_s=t_end - t_dev,
-                            total_s=t_end - t_start)}
+            "timings": timings(st, t_dev, t_end)}

@@ -35,12 +35,12 @@ over its genes of z_g / sqrt(m2_g / n).  Out of scope: weighted, radius or symme
 cross terms between time points, other clusterings.
 
 Limits: 1 to 4096 selected genes; at most 2147483647 spots and edges per time point; permutation indices below 2^32."""
-import os
 import sys
 import time
 
 import numpy as np
 
+from .moran import centre_spread, columns, degenerate, edge_csr, gene_selection, open_stage, read_genes, timings, top_genes
 from .utils._stage_utils import edge_pair, labeling_runs, savez_pinned
 
 FIELDS = ("R", "z_sim", "p_sim", "padj")
@@ -86,59 +86,40 @@ class _Images:
     """Z and Y of a call on the device with what the launches take."""
 
 
-def _images(edges, data, values, centre, genes):
-    """The images of a call (module docstring): a DeviceCounts goes through spadot_cross_dense's CSC part, dense columns enter as
-    Z directly.  Every refusal comes before any launch."""
+def _images(edges, cols, centre, genes):
+    """The images of a call (module docstring) over the Columns `cols`: a DeviceCounts goes through spadot_cross_dense's CSC
+    part, dense columns enter as Z directly.  Every refusal comes before any launch."""
     import torch
     from . import stage_ops as ops
-    from .hotspots import _csr, _selection
     im = _Images()
-    if hasattr(data, "colptr"):
-        dc = data
-        T, G, dev = int(dc.T), int(dc.G), dc.device
-        off = np.asarray(dc.tp_off_host, dtype=np.int64)
-        if not isinstance(values, torch.Tensor):
-            raise RuntimeError("cross_sums takes the values as a device tensor (torch), not a host array")
-    else:
-        dc = None
-        if values is not None:
-            raise ValueError("values go with a DeviceCounts; dense columns are their own values")
-        if not data or any(not isinstance(x, torch.Tensor) for x in data):
-            raise RuntimeError("cross_sums takes a DeviceCounts or one dense device tensor [n, C] per time point")
-        for t, x in enumerate(data):
-            if not x.is_cuda:
-                raise RuntimeError("spadot_amd takes the cross sums on the MI355X only (got a CPU tensor); there is no CPU path")
-            if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] != data[0].shape[1] or x.dtype not in (torch.float32, torch.float64):
-                raise ValueError(f"the columns of time point {t} must be a float32 or float64 tensor [n, C] (got {tuple(x.shape)} "
-                                 f"{x.dtype})")
-        T, G, dev = len(data), int(data[0].shape[1]), data[0].device
-        off = np.concatenate([[0], np.cumsum([int(x.shape[0]) for x in data])]).astype(np.int64)
+    T, G, dev = cols.T, cols.G, cols.device
+    off = np.asarray(cols.tp_off_host, dtype=np.int64)
     if not edges or len(edges) != T:
         raise ValueError(f"cross_sums takes one edge list per time point ({len(edges) if edges else 0} lists, {T} time points)")
     pairs = [edge_pair(e, dev, t) for t, e in enumerate(edges)]
     centre = centre if isinstance(centre, torch.Tensor) else torch.as_tensor(np.asarray(centre, dtype=np.float64), device=dev)
     if tuple(centre.shape) != (T, G) or centre.dtype != torch.float64:
         raise ValueError(f"centre must be fp64 [T, G] = [{T}, {G}] (got {tuple(centre.shape)} {centre.dtype})")
-    sel = _selection(genes, G)
+    sel = gene_selection(genes, G)
     if sel.size > ops.CROSS_MAX_G:
         raise ValueError(f"cross_sums takes at most {ops.CROSS_MAX_G} selected genes (got {sel.size})")
     sizes = np.diff(off)
     with torch.cuda.device(dev):
-        rowptr, col, d8 = _csr(pairs, sizes, dev)
+        rowptr, col, d8 = edge_csr(pairs, sizes, dev)
         desc = np.zeros((T, ops.CROSS_DESC), dtype=np.int64)
         desc[:, :8] = d8
         desc[:, 3] = off[:-1]
         zoff, zrows = ops.cross_layout(sizes)
         desc[:, 8] = zoff
         centre = centre.contiguous()
-        if dc is not None:
+        if cols.dense is None:
             gsel = torch.as_tensor(sel, device=dev)
-            args = (rowptr, col, dc.colptr, dc.ridx, values, centre, gsel)
+            args = (rowptr, col, cols.colptr, cols.ridx, cols.values, centre, gsel)
             Z, Y = ops.cross_dense_launch(*args, ops.cross_dense_check(*args, desc))
         else:
             gl = torch.as_tensor(sel.astype(np.int64), device=dev)
             Z = torch.zeros((zrows, ops.cross_padded(sel.size)), dtype=torch.float64, device=dev)
-            for t, x in enumerate(data):                     # fp32 values promoted, minus the centre: the bits of the CSC part
+            for t, x in enumerate(cols.dense):               # fp32 values promoted, minus the centre: the bits of the CSC part
                 Z[int(zoff[t]):int(zoff[t]) + int(sizes[t]), :sel.size] = \
                     x[:, gl].to(torch.float32).to(torch.float64) - centre[t, gl][None, :]
             args = (rowptr, col, None, None, None, None, int(sel.size))
@@ -174,9 +155,11 @@ def cross_sums(edges, data, values, centre, genes, n_perms, seed=0, first=0, obs
     n_perms, first, observed = int(n_perms), int(first), bool(observed)
     if n_perms < 0:
         raise ValueError(f"the number of permutations must not be negative (got n_perms = {n_perms})")
-    from .stage_ops import _labelings
-    _labelings("cross_sums", observed, first, n_perms)       # ahead of the launches that build the images
-    im = _images(edges, data, values, centre, genes)
+    from .stage_ops import labelings
+    labelings("cross_sums", observed, first, n_perms)        # ahead of the launches that build the images
+    if hasattr(data, "colptr") and not isinstance(values, torch.Tensor):
+        raise RuntimeError("cross_sums takes the values as a device tensor (torch), not a host array")
+    im = _images(edges, columns(data, values), centre, genes)
     M = torch.cat([m for _, _, _, m in _runs(im, n_perms, seed, first, observed)], dim=1).cpu().numpy()
     out = [M[t] for t in range(im.T)]
     if not images:
@@ -193,35 +176,18 @@ def cross_moran(edges, data, genes, values=None, n_perms=100, seed=0):
     The fold of the sums into B, the comparison and the counts are torch ops on the device, run by run: no [P, genes, genes] block
     goes to the host.  Returns [t] -> CrossResult."""
     import torch
-    from .autocorr import _dense_csc, _moments
-    from .hotspots import _selection
     n_perms = int(n_perms)
     if n_perms < 0:
         raise ValueError(f"the number of permutations must not be negative (got n_perms = {n_perms})")
-    if hasattr(data, "colptr"):
-        dc, source = data, data
-        if values is None:
-            from .trends import lognorm_values
-            values = lognorm_values(dc)
-        vals = values
-    else:
-        if values is not None:
-            raise ValueError("values go with a DeviceCounts; dense columns are their own values")
-        dev = data[0].device if data and isinstance(data[0], torch.Tensor) else None
-        dc, vals = _dense_csc(data, dev)                     # the checks and the moments of the dense columns
-        source = data
-    sel = _selection(genes, int(dc.G))
-    off = np.asarray(dc.tp_off_host, dtype=np.int64)
-    with torch.cuda.device(dc.device):
-        _, S1, S2 = _moments(dc, vals)
-        n_t = torch.as_tensor(np.diff(off).astype(np.float64), device=dc.device)[:, None]
-        centre = (S1 / n_t).contiguous()
-        m2 = torch.clamp(S2 - S1 * S1 / n_t, min=0.0)
-        im = _images(edges, source, values, centre, sel)
+    cols = columns(data, values)
+    sel = gene_selection(genes, cols.G)
+    with torch.cuda.device(cols.device):
+        _, centre, m2, S2 = centre_spread(cols)
+        im = _images(edges, cols, centre, sel)
         G = int(sel.size)
         B0 = None
-        ge = torch.zeros((im.T, G, G), dtype=torch.int64, device=dc.device)
-        s1 = torch.zeros((im.T, G, G), dtype=torch.float64, device=dc.device)
+        ge = torch.zeros((im.T, G, G), dtype=torch.int64, device=cols.device)
+        s1 = torch.zeros((im.T, G, G), dtype=torch.float64, device=cols.device)
         s2 = torch.zeros_like(s1)
         for obs, _p0, npm, M in _runs(im, n_perms, seed, 0, True):
             B = 0.5 * (M + M.transpose(2, 3))
@@ -238,9 +204,9 @@ def cross_moran(edges, data, genes, values=None, n_perms=100, seed=0):
     res = []
     for t in range(im.T):
         n, E = int(im.sizes[t]), im.E[t]
-        bad = np.full(G, True) if n < 3 or E == 0 else ~(m2[t] > n * 2.0 ** -50 * S2[t])
         z = im.Z[int(im.zoff[t]):int(im.zoff[t]) + n, :G]
-        res.append(CrossResult(B0[t], ge[t], s1[t], s2[t], centre[t], m2[t], n, E, n_perms, bad, sel, z))
+        res.append(CrossResult(B0[t], ge[t], s1[t], s2[t], centre[t], m2[t], n, E, n_perms,
+                               degenerate(n, E, m2[t], S2[t]), sel, z))
     return res
 
 
@@ -372,10 +338,6 @@ def modules(args):
     'timepoints', 'timings'}."""
     import torch
     from .autocorr import spatial_autocorr
-    from .hotspots import read_genes
-    from .markers import load_marker_counts
-    from .neighbors import spatial_edges
-    from .preprocess import DeviceCounts
     from .trends import lognorm_values
     t_start = time.perf_counter()
 
@@ -390,40 +352,19 @@ def modules(args):
         raise ValueError(f"the modules stage takes top >= 1, k >= 1, n_perms >= 1, min_sim <= 1, min_genes >= 1, 0 < alpha <= 1 and "
                          f"top_pairs >= 0 (got top = {top}, k = {k}, n_perms = {n_perms}, min_sim = {min_sim}, min_genes = "
                          f"{min_genes}, alpha = {alpha}, top_pairs = {top_pairs})")
-    device = getattr(args, "device", None) or "cuda:0"
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("spadot_amd takes the gene modules on the MI355X only (device 'cuda:N'); there is no CPU path")
-    raw, path = load_marker_counts(args.data)
-    sel = read_genes(args.genes, raw.var_names) if getattr(args, "genes", None) else None
-    if not getattr(args, "output_dir", None):
-        args.output_dir = os.path.dirname(path) if path else os.getcwd()
-    os.makedirs(args.output_dir, exist_ok=True)
-    prefix = getattr(args, "prefix", "") or ""
-    dc = DeviceCounts(raw, dev)
-    if not np.all(np.isfinite(dc.spatial)):
-        raise ValueError("the data holds spots without finite spatial coordinates")
-    tps = [str(t) for t in dc.tps]
-    off = dc.tp_off_host
-    t_read = time.perf_counter()
-    edges = [spatial_edges(dc.spatial[int(off[t]):int(off[t + 1])], k, dev) for t in range(dc.T)]
-    torch.cuda.synchronize(dev)
-    t_graph = time.perf_counter()
-    with torch.cuda.device(dev):
+    st = open_stage(args, k, "the gene modules", t_start,
+                    lambda raw: read_genes(args.genes, raw.var_names) if getattr(args, "genes", None) else None)
+    sel, dc, tps = st.extras, st.dc, st.tps
+    with torch.cuda.device(st.dev):
         values = lognorm_values(dc)
         if sel is None:                                      # the top genes by Moran's I of every time point, unioned
-            glob = spatial_autocorr(edges, dc, values, n_perms=0)
-            picked = set()
-            for r in glob:
-                order = np.lexsort((np.arange(dc.G), -np.where(np.isnan(r.I), -np.inf, r.I)))
-                picked.update(int(g) for g in order[:top] if not np.isnan(r.I[g]))
-            if not picked:
+            sel = top_genes(spatial_autocorr(st.edges, dc, values, n_perms=0), top)
+            if not sel.size:
                 raise ValueError("no gene has a Moran's I in any time point: nothing to group")
-            sel = np.asarray(sorted(picked), dtype=np.int32)
-        res = cross_moran(edges, dc, sel, values, n_perms=n_perms, seed=seed)
+        res = cross_moran(st.edges, dc, sel, values, n_perms=n_perms, seed=seed)
         labels = [gene_modules(r.R, ~r.degenerate, min_sim, min_genes) for r in res]
         scores = [module_scores(r.z, r.m2, r.n, lab) for r, lab in zip(res, labels)]
-    torch.cuda.synchronize(dev)
+    torch.cuda.synchronize(st.dev)
     t_dev = time.perf_counter()
     tables, pair_tables = {}, {}
     arrays = dict(timepoints=np.asarray(tps), genes=np.asarray(dc.genes).astype(str)[sel], k=np.int64(k), n_perms=np.int64(n_perms),
@@ -431,23 +372,22 @@ def modules(args):
     significant = 0
     for t, (tp, r) in enumerate(zip(tps, res)):
         tables[tp] = module_table(r, dc.genes, labels[t])
-        tables[tp].to_csv(os.path.join(args.output_dir, f"{prefix}modules_{tp}.csv"), index=False)
+        tables[tp].to_csv(st.path(f"modules_{tp}.csv"), index=False)
         pair_tables[tp] = pair_table(r, dc.genes, labels[t], top_pairs)
-        pair_tables[tp].to_csv(os.path.join(args.output_dir, f"{prefix}modules_pairs_{tp}.csv"), index=False)
+        pair_tables[tp].to_csv(st.path(f"modules_pairs_{tp}.csv"), index=False)
         for name in FIELDS:
             arrays[f"{tp}_{name}"] = getattr(r, name)
         arrays[f"{tp}_module"], arrays[f"{tp}_scores"] = labels[t], scores[t]
-        arrays[f"{tp}_spots"] = np.asarray(dc.perm[int(off[t]):int(off[t + 1])], dtype=np.int64)
+        arrays[f"{tp}_spots"] = np.asarray(dc.perm[st.rows(t)], dtype=np.int64)
         with np.errstate(invalid="ignore"):
             significant += int((r.padj[np.triu_indices(sel.size, 1)] <= alpha).sum())
     overlap = overlap_table(tps, labels)
-    overlap.to_csv(os.path.join(args.output_dir, f"{prefix}modules_overlap.csv"), index=False)
-    savez_pinned(os.path.join(args.output_dir, prefix + "modules.npz"), arrays)
+    overlap.to_csv(st.path("modules_overlap.csv"), index=False)
+    savez_pinned(st.path("modules.npz"), arrays)
     t_end = time.perf_counter()
     print(f"modules: {sel.size} genes x {dc.n} spots of {dc.T} time points, k = {k}, {n_perms} permutations, "
           f"{sum(int(lab.max()) + 1 for lab in labels)} modules, {significant} pairs with padj <= {alpha}, written to "
           f"{args.output_dir}", file=sys.stderr)
     return {"tables": tables, "pair_tables": pair_tables, "overlap": overlap, "results": dict(zip(tps, res)),
             "modules": dict(zip(tps, labels)), "scores": dict(zip(tps, scores)), "genes": sel, "timepoints": tps,
-            "timings": dict(read_s=t_read - t_start, graph_s=t_graph - t_read, device_s=t_dev - t_graph, write_s=t_end - t_dev,
-                            total_s=t_end - t_start)}
+            "timings": timings(st, t_dev, t_end)}

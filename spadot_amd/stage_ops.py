@@ -66,7 +66,47 @@ def _csc_sizes(colptr, ridx, values, limit):
     return G, nnz
 
 
-def _labelings(name, observed, first, P):
+def _csr_stats(rowptr, col, desc, zero):
+    """Per time point of a descriptor whose columns 0, 1, 2 and 5 are eoff, n, E and roff: [smallest neighbour in col, largest,
+    rowptr[0], rowptr[-1], rowptr descends somewhere] as 0-d int64 device tensors."""
+    stats = []
+    for eoff, n, E, _row0, _gid, roff, *_rest in desc.tolist():
+        rp = rowptr[roff:roff + n + 1]
+        lo, hi = torch.aminmax(col[eoff:eoff + E]) if E > 0 else (zero, zero)
+        stats += [lo.long(), hi.long(), rp[0].long(), rp[-1].long(), (rp[1:] < rp[:-1]).any().long()]
+    return stats
+
+
+def _refuse_csr(desc, per):
+    """per: the numbers of _csr_stats on the host, [T, 5]; columns 6 and 7 of the descriptor, the range of col, are filled in."""
+    desc[:, 6], desc[:, 7] = per[:, 0], per[:, 1]
+    for t in range(desc.shape[0]):
+        n, E = int(desc[t, 1]), int(desc[t, 2])
+        if E > 0 and (per[t, 0] < 0 or per[t, 1] >= n):
+            raise ValueError(f"time point {t} has neighbours {int(per[t, 0])} .. {int(per[t, 1])} in col: they must lie in 0 .. "
+                             f"{n - 1}")
+        if per[t, 2] != 0 or per[t, 3] != E or per[t, 4]:
+            raise ValueError(f"the rowptr of time point {t} must ascend from 0 to its {E} edges (it runs from {int(per[t, 2])} to "
+                             f"{int(per[t, 3])})")
+
+
+def _refuse_genes(gene_lo, gene_hi, G):
+    if gene_lo < 0 or gene_hi >= G:
+        raise ValueError(f"the selected genes {gene_lo} .. {gene_hi} must lie in 0 .. {G - 1}")
+
+
+def _refuse_time_point(t, name, row, n, E, most, consistent):
+    """The limits of one row of a descriptor of time points: 1 .. most spots, 0 .. most edges, and what the caller found of
+    its other columns."""
+    if not 1 <= n <= most:
+        raise ValueError(f"time point {t} has {n} spots: {name} takes 1 to {most} (int32 spot numbers)")
+    if not 0 <= E <= most:
+        raise ValueError(f"time point {t} has {E} edges: {name} takes at most {most} per time point")
+    if not consistent:
+        raise ValueError(f"time point {t}: inconsistent descriptor {row}")
+
+
+def labelings(name, observed, first, P):
     """(observed as 0 / 1, first, P) of a call over the observed labeling and / or the permutations first .. first + P - 1."""
     observed, first, P = int(bool(observed)), int(first), int(P)
     if P < 0 or first < 0 or observed + P < 1:
@@ -333,15 +373,11 @@ def autocorr_check(src, dst, colptr, ridx, values, centre, desc, g0, ng, observe
         raise ValueError(f"centre must be [T, G] = [{T}, {G}] (got {tuple(centre.shape)})")
     if g0 < 0 or ng < 1 or g0 + ng > G:
         raise ValueError(f"the genes {g0} .. {g0 + ng - 1} are not a range of the {G} genes")
-    observed, first, P = _labelings("autocorr_sums", observed, first, P)
+    observed, first, P = labelings("autocorr_sums", observed, first, P)
     rows = 0
     for t, (eoff, n, E, row0, gid, _lo, _hi) in enumerate(desc.tolist()):
-        if not 1 <= n <= AUTOCORR_MAX:
-            raise ValueError(f"time point {t} has {n} spots: spadot_autocorr_sums takes 1 to {AUTOCORR_MAX} (int32 spot numbers)")
-        if not 0 <= E <= AUTOCORR_MAX:
-            raise ValueError(f"time point {t} has {E} edges: spadot_autocorr_sums takes at most {AUTOCORR_MAX} per time point")
-        if eoff < 0 or not 0 <= row0 <= AUTOCORR_MAX or not 0 <= gid <= AUTOCORR_MAX:
-            raise ValueError(f"time point {t}: inconsistent descriptor {desc[t].tolist()}")
+        _refuse_time_point(t, "spadot_autocorr_sums", desc[t].tolist(), n, E, AUTOCORR_MAX,
+                           eoff >= 0 and 0 <= row0 <= AUTOCORR_MAX and 0 <= gid <= AUTOCORR_MAX)
         if eoff + E > src.numel() or eoff + E > dst.numel():
             raise ValueError(f"time point {t}: its edges reach past the end of the tensors")
         rows = max(rows, row0 + n)
@@ -447,7 +483,7 @@ def ligrec_check(colptr, ridx, values, labels, genes, desc, K, observed, first, 
     if ng < 1 or gc < 1:
         raise ValueError(f"spadot_ligrec_sums takes at least one selected gene and gene_chunk >= 1 (got {ng} genes, gene_chunk = "
                          f"{gc})")
-    observed, first, P = _labelings("ligrec_sums", observed, first, P)
+    observed, first, P = labelings("ligrec_sums", observed, first, P)
     rows = 0
     for t, (n, row0, gid) in enumerate(desc.tolist()):
         if not 1 <= n <= LIGREC_MAX:
@@ -466,8 +502,7 @@ def ligrec_check(colptr, ridx, values, labels, genes, desc, K, observed, first, 
     _refuse_rows(ridx_lo, ridx_hi, nnz, rows)
     if label_hi >= K:
         raise ValueError(f"labels holds the label {label_hi}: labels must lie in 0 .. {K - 1}")
-    if gene_lo < 0 or gene_hi >= G:
-        raise ValueError(f"the selected genes {gene_lo} .. {gene_hi} must lie in 0 .. {G - 1}")
+    _refuse_genes(gene_lo, gene_hi, G)
     _refuse_colptr(c0, c1, unordered, nnz)
     return desc, ridx_lo, ridx_hi, label_hi, gene_lo, gene_hi
 
@@ -584,42 +619,23 @@ def local_check(rowptr, col, colptr, ridx, values, centre, genes, desc, first, P
                          f"perm_chunk >= 1 (got {ng} genes, threads = {threads}, gs = {gs}, perm_chunk = {chunk})")
     if int(P) < 1:
         raise ValueError(f"local_lag takes P >= 1 permutations (got P = {int(P)})")
-    _, first, P = _labelings("local_lag", False, first, P)
+    _, first, P = labelings("local_lag", False, first, P)
     rows = 0
     for t, (eoff, n, E, row0, gid, roff, _lo, _hi) in enumerate(desc.tolist()):
-        if not 1 <= n <= LOCAL_MAX:
-            raise ValueError(f"time point {t} has {n} spots: spadot_local_lag takes 1 to {LOCAL_MAX} (int32 spot numbers)")
-        if not 0 <= E <= LOCAL_MAX:
-            raise ValueError(f"time point {t} has {E} edges: spadot_local_lag takes at most {LOCAL_MAX} per time point")
-        if eoff < 0 or roff < 0 or not 0 <= row0 <= LOCAL_MAX or not 0 <= gid <= LOCAL_MAX:
-            raise ValueError(f"time point {t}: inconsistent descriptor {desc[t].tolist()}")
+        _refuse_time_point(t, "spadot_local_lag", desc[t].tolist(), n, E, LOCAL_MAX,
+                           eoff >= 0 and roff >= 0 and 0 <= row0 <= LOCAL_MAX and 0 <= gid <= LOCAL_MAX)
         if eoff + E > col.numel() or roff + n + 1 > rowptr.numel():
             raise ValueError(f"time point {t}: its rows or edges reach past the end of the tensors")
         rows = max(rows, row0 + n)
     if T * -(-P // (chunk or LOCAL_CHUNK)) * -(-ng // (gs or LOCAL_GS)) > LOCAL_MAX:
         raise ValueError(f"the call holds more than {LOCAL_MAX} workgroups (the grid of one launch)")
     zero = torch.zeros((), dtype=torch.int64, device=colptr.device)
-    stats = []
-    for eoff, n, E, _row0, _gid, roff, _lo, _hi in desc.tolist():
-        rp = rowptr[roff:roff + n + 1]
-        lo, hi = torch.aminmax(col[eoff:eoff + E]) if E > 0 else (zero, zero)
-        stats += [lo.long(), hi.long(), rp[0].long(), rp[-1].long(), (rp[1:] < rp[:-1]).any().long()]
-    stats += _csc_stats(colptr, ridx, zero) + [s.long() for s in torch.aminmax(genes)]
+    stats = _csr_stats(rowptr, col, desc, zero) + _csc_stats(colptr, ridx, zero) + [s.long() for s in torch.aminmax(genes)]
     stats = torch.stack(stats).cpu().numpy()                                # the one host round trip ahead of the launch
-    per = stats[:5 * T].reshape(T, 5)
-    desc[:, 6], desc[:, 7] = per[:, 0], per[:, 1]
-    for t in range(T):
-        n, E = int(desc[t, 1]), int(desc[t, 2])
-        if E > 0 and (per[t, 0] < 0 or per[t, 1] >= n):
-            raise ValueError(f"time point {t} has neighbours {int(per[t, 0])} .. {int(per[t, 1])} in col: they must lie in 0 .. "
-                             f"{n - 1}")
-        if per[t, 2] != 0 or per[t, 3] != E or per[t, 4]:
-            raise ValueError(f"the rowptr of time point {t} must ascend from 0 to its {E} edges (it runs from {int(per[t, 2])} to "
-                             f"{int(per[t, 3])})")
+    _refuse_csr(desc, stats[:5 * T].reshape(T, 5))
     ridx_lo, ridx_hi, c0, c1, unordered, gene_lo, gene_hi = (int(v) for v in stats[5 * T:])
     _refuse_rows(ridx_lo, ridx_hi, nnz, rows)
-    if gene_lo < 0 or gene_hi >= G:
-        raise ValueError(f"the selected genes {gene_lo} .. {gene_hi} must lie in 0 .. {G - 1}")
+    _refuse_genes(gene_lo, gene_hi, G)
     _refuse_colptr(c0, c1, unordered, nnz)
     return desc, ridx_lo, ridx_hi, gene_lo, gene_hi
 
@@ -706,12 +722,8 @@ def _cross_desc(desc, ng, name):
         raise ValueError(f"{name} takes 1 to {CROSS_MAX_G} selected genes (got {ng})")
     need = 0
     for t, (eoff, n, E, row0, gid, roff, _lo, _hi, zoff) in enumerate(desc.tolist()):
-        if not 1 <= n <= CROSS_MAX:
-            raise ValueError(f"time point {t} has {n} spots: {name} takes 1 to {CROSS_MAX} (int32 spot numbers)")
-        if not 0 <= E <= CROSS_MAX:
-            raise ValueError(f"time point {t} has {E} edges: {name} takes at most {CROSS_MAX} per time point")
-        if eoff < 0 or roff < 0 or zoff < 0 or not 0 <= row0 <= CROSS_MAX or not 0 <= gid <= CROSS_MAX:
-            raise ValueError(f"time point {t}: inconsistent descriptor {desc[t].tolist()}")
+        _refuse_time_point(t, name, desc[t].tolist(), n, E, CROSS_MAX,
+                           eoff >= 0 and roff >= 0 and zoff >= 0 and 0 <= row0 <= CROSS_MAX and 0 <= gid <= CROSS_MAX)
         need = max(need, zoff + (n + 3) // 4 * 4)
     return desc, need
 
@@ -756,24 +768,11 @@ def cross_dense_check(rowptr, col, colptr, ridx, values, centre, genes, desc, Z=
     if -(-need * cross_padded(ng) // 256) > CROSS_MAX:
         raise ValueError(f"the images hold more than {CROSS_MAX} workgroups of 256 cells (the grid of one launch)")
     zero = torch.zeros((), dtype=torch.int64, device=rowptr.device)
-    stats = []
-    for eoff, n, E, _row0, _gid, roff, _lo, _hi, _zoff in desc.tolist():
-        rp = rowptr[roff:roff + n + 1]
-        lo, hi = torch.aminmax(col[eoff:eoff + E]) if E > 0 else (zero, zero)
-        stats += [lo.long(), hi.long(), rp[0].long(), rp[-1].long(), (rp[1:] < rp[:-1]).any().long()]
+    stats = _csr_stats(rowptr, col, desc, zero)
     if csc:
         stats += _csc_stats(colptr, ridx, zero) + [s.long() for s in torch.aminmax(genes)]
     stats = torch.stack(stats).cpu().numpy()                                # the one host round trip ahead of the launch
-    per = stats[:5 * T].reshape(T, 5)
-    desc[:, 6], desc[:, 7] = per[:, 0], per[:, 1]
-    for t in range(T):
-        n, E = int(desc[t, 1]), int(desc[t, 2])
-        if E > 0 and (per[t, 0] < 0 or per[t, 1] >= n):
-            raise ValueError(f"time point {t} has neighbours {int(per[t, 0])} .. {int(per[t, 1])} in col: they must lie in 0 .. "
-                             f"{n - 1}")
-        if per[t, 2] != 0 or per[t, 3] != E or per[t, 4]:
-            raise ValueError(f"the rowptr of time point {t} must ascend from 0 to its {E} edges (it runs from {int(per[t, 2])} to "
-                             f"{int(per[t, 3])})")
+    _refuse_csr(desc, stats[:5 * T].reshape(T, 5))
     ridx_lo = ridx_hi = gene_lo = gene_hi = 0
     if csc:
         ridx_lo, ridx_hi, c0, c1, unordered, gene_lo, gene_hi = (int(v) for v in stats[5 * T:])
@@ -833,7 +832,7 @@ def cross_check(Z, Y, desc, ng, observed, first, P):
     descriptor; ValueError otherwise."""
     need_cuda(Z, Y)
     desc, need = _cross_desc(desc, ng, "spadot_cross_sums")
-    observed, first, P = _labelings("cross_sums", observed, first, P)
+    observed, first, P = labelings("cross_sums", observed, first, P)
     zrows = int(Z.shape[0]) if Z.dim() == 2 else -1
     _cross_image(Z, "Z", zrows, cross_padded(ng))
     _cross_image(Y, "Y", zrows, cross_padded(ng))

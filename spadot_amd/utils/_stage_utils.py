@@ -1,4 +1,5 @@
-"""What the analysis stages (neighbors, cooccurrence, autocorr, ligrec) share on the host."""
+"""What the analysis stages (neighbors, cooccurrence, autocorr, ligrec, hotspots, modules, ripley) share on the host.  What only
+the three Moran stages share is in spadot_amd/moran.py."""
 import zipfile
 
 import numpy as np

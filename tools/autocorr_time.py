@@ -96,7 +96,8 @@ def main():
     a = ap.parse_args()
     import torch
     from spadot_amd import stage_ops as ops
-    from spadot_amd.autocorr import _moments, autocorr_sums, spatial_autocorr
+    from spadot_amd.autocorr import autocorr_sums, spatial_autocorr
+    from spadot_amd.moran import centre_spread, columns
     from spadot_amd.neighbors import spatial_edges
     from spadot_amd.preprocess import DeviceCounts
     from spadot_amd.trends import lognorm_values
@@ -113,8 +114,7 @@ def main():
         torch.cuda.synchronize()
         graph_ms = (time.perf_counter() - t0) * 1e3
         values = lognorm_values(dc)
-        S0, S1, _ = _moments(dc, values)
-        centre = (S1 / torch.as_tensor(np.diff(off).astype(np.float64), device=dc.device)[:, None]).contiguous()
+        centre = centre_spread(columns(dc, values))[1]
         return dc, edges, values, centre, graph_ms
 
     spatial_edges(rng.uniform(size=(64, 2)), a.k, dev)                               # warm

@@ -47,8 +47,8 @@ def main():
     a = ap.parse_args()
     import torch
     from spadot_amd import stage_ops as ops
-    from spadot_amd.autocorr import _moments
-    from spadot_amd.hotspots import _csr, local_moran
+    from spadot_amd.hotspots import local_moran
+    from spadot_amd.moran import centre_spread, columns, edge_csr
     from spadot_amd.neighbors import spatial_edges
     from spadot_amd.preprocess import DeviceCounts
     from spadot_amd.trends import lognorm_values
@@ -60,13 +60,12 @@ def main():
     off = dc.tp_off_host.astype(np.int64)
     edges = [spatial_edges(dc.spatial[int(off[t]):int(off[t + 1])], a.k, dev) for t in range(dc.T)]
     values = lognorm_values(dc)
-    _, S1, _ = _moments(dc, values)
-    centre = (S1 / torch.as_tensor(np.diff(off).astype(np.float64), device=dc.device)[:, None]).contiguous()
+    centre = centre_spread(columns(dc, values))[1]
     shape = f"{a.tps} x {a.n} spots x {a.genes} genes, k = {a.k}, {a.perms} permutations"
     E = sum(int(s.shape[0]) for s, _ in edges)
     terms = E * a.genes * (a.perms + 1)
 
-    rowptr, col, desc = _csr(edges, np.diff(off), dc.device)
+    rowptr, col, desc = edge_csr(edges, np.diff(off), dc.device)
     desc[:, 3] = off[:-1]
     gsel = torch.arange(a.genes, dtype=torch.int32, device=dev)
     args = (rowptr, col, dc.colptr, dc.ridx, values, centre, gsel)

@@ -52,8 +52,7 @@ def main():
     import torch
     from spadot_amd import modules
     from spadot_amd import stage_ops as ops
-    from spadot_amd.autocorr import _moments
-    from spadot_amd.hotspots import _csr
+    from spadot_amd.moran import centre_spread, columns, edge_csr
     from spadot_amd.neighbors import spatial_edges
     from spadot_amd.preprocess import DeviceCounts
     from spadot_amd.trends import lognorm_values
@@ -66,13 +65,12 @@ def main():
     off = dc.tp_off_host.astype(np.int64)
     edges = [spatial_edges(dc.spatial[int(off[t]):int(off[t + 1])], a.k, dev) for t in range(dc.T)]
     values = lognorm_values(dc)
-    _, S1, _ = _moments(dc, values)
-    centre = (S1 / torch.as_tensor(np.diff(off).astype(np.float64), device=dc.device)[:, None]).contiguous()
+    centre = centre_spread(columns(dc, values))[1]
     shape = f"{a.tps} x {a.n} spots x {a.genes} genes, k = {a.k}, {a.perms} permutations"
     L = a.perms + 1
     fmas = int(dc.n) * a.genes * a.genes * L
 
-    rowptr, col, d8 = _csr(edges, np.diff(off), dc.device)
+    rowptr, col, d8 = edge_csr(edges, np.diff(off), dc.device)
     desc = np.zeros((dc.T, ops.CROSS_DESC), dtype=np.int64)
     desc[:, :8] = d8
     desc[:, 3] = off[:-1]
