@@ -22,6 +22,7 @@
  *   spadot_weighted_moments  no counterpart in the reference: X_csc.T @ W of the log-normalised counts, three moments
  *   spadot_nhood_counts      no counterpart in the reference: the label-pair edge counts of squidpy's gr.nhood_enrichment
  *   spadot_cooccur_counts    no counterpart in the reference: the label-pair counts by distance of squidpy's gr.co_occurrence
+ *   spadot_cooccur_null      no counterpart in the reference: the same counts under relabelings (a random-labelling null)
  *   spadot_ripley_*          no counterpart in the reference: the pair, nearest-neighbour and empty-space counts of squidpy's gr.ripley
  *   spadot_local_lag         no counterpart in the reference: the neighbour sums and permutation counts of esda's Moran_Local
  *   spadot_cross_*           no counterpart in the reference: the cross sums of a bivariate Moran's I between genes (esda's Moran_BV)
@@ -762,6 +763,24 @@ int spadot_nhood_counts(const int *src, const int *dst, const unsigned char *lab
  * refuse (the labels never reach the library: the offsets do). */
 int spadot_cooccur_counts(const double *xy, const long long *desc_host, const long long *desc_dev, const double *r2_host,
                           const double *r2_dev, int P, int K_max, int B_max, long long *out, void *stream);
+
+/* The random-labelling null of the counts above (restated in numpy in tests/cooccur_null_ref.py): the same
+ * counts of the observed labeling and of relabelings of every problem in ONE launch.  Pattern 0 is the observed labeling;
+ * pattern s >= 1 leaves the labels on the sorted positions and gives position j the coordinates xy[pi^-1(j)], pi the
+ * permutation of spadot_nhood_counts with (seed, g, s - 1, n) -- the convention of spadot_ripley_counts under null "labels".
+ * pi^-1 is evaluated per element while the spots are read: no permuted copy of xy and no table of pi exists.  The domain
+ * sizes are those of the observed labeling in every pattern.
+ * xy, desc, r2 as for spadot_cooccur_counts, with the problem number g of a problem in column 37 of its descriptor (K <= 32
+ * leaves the columns 37 .. 39 free).  The call counts pattern 0 where observed = 1, then the patterns 1 + first ..
+ * first + n_perms.
+ * out: int64 [P, observed + n_perms, K_max, K_max, B_max], written completely (zeros too).  Integers only: a problem gives the
+ * same integers alone, in any batch, run after run, under a larger K_max or B_max and under any split of the relabelings
+ * into calls with `first` advanced.
+ * Return as spadot_cooccur_counts, and -22 for observed not 0 or 1, -7 for observed + n_perms outside 1 .. 65535 (gridDim.y;
+ * the problems are gridDim.z), first < 0, first + n_perms > 2^31, or g outside 0 .. 2147483647. */
+int spadot_cooccur_null(const double *xy, const long long *desc_host, const long long *desc_dev, const double *r2_host,
+                        const double *r2_dev, int P, int K_max, int B_max, int observed, long long first, int n_perms,
+                        long long seed, long long *out, void *stream);
 
 /* ---------------------------------------------------------------- Ripley's L, G and F per domain (csrc/ripley.hip)
  * The integers behind Ripley's functions of every (problem, domain, pattern) of a call in ONE counting launch; the definition

@@ -9,7 +9,8 @@
     python -m spadot_amd score   -i LATENT --domains CSV [-o DIR] [--prefix P] [--device cuda:0]
     python -m spadot_amd trends  -i COUNTS [--trajectories NPZ] [--fates NPZ] [-o DIR] [--prefix P] [--top 100] [--device cuda:0]
     python -m spadot_amd neighbors --domains CSV [-o DIR] [--prefix P] [--k 6] [--n_perms 1000] [--seed 0] [--device cuda:0]
-    python -m spadot_amd cooccurrence --domains CSV [-o DIR] [--prefix P] [--bins 50] [--radius R] [--ring] [--device cuda:0]
+    python -m spadot_amd cooccurrence --domains CSV [-o DIR] [--prefix P] [--bins 50] [--radius R] [--ring] [--n_perms 0]
+                                      [--seed 0] [--alpha 0.05] [--device cuda:0]
     python -m spadot_amd autocorr -i COUNTS [-o DIR] [--prefix P] [--k 6] [--n_perms 100] [--seed 0] [--top 100] [--device cuda:0]
     python -m spadot_amd hotspots -i COUNTS [-o DIR] [--prefix P] [--k 6] [--n_perms 999] [--seed 0] [--genes A,B | FILE] [--top 50]
                                   [--alpha 0.05] [--fdr] [--domains CSV] [--device cuda:0]
@@ -38,7 +39,9 @@ k-nearest-neighbour graph of every time point, the neighbourhood-enrichment perm
 own domain (spadot_amd.neighbors).  `cooccurrence` reads the same table: for every time point, every ordered pair of
 domains and a ladder of radii up to a quarter of the tissue's diagonal (or `--radius`), the number of pairs of spots within that
 distance and the co-occurrence ratio, which tells how far an association reaches; `--ring` takes the pairs between consecutive
-radii instead of those within each (spadot_amd.cooccurrence).  `autocorr` reads the counts and their coordinates: on the
+radii instead of those within each (spadot_amd.cooccurrence); with `--n_perms S` the counts of every pair are also
+tested against S random relabelings of the spots: an envelope per radius, pointwise and global p-values, and a verdict `attract`,
+`avoid` or `independent` per pair of domains -- a verdict on the joint labelling, not on an interaction.  `autocorr` reads the counts and their coordinates: on the
 k-nearest-neighbour graph of every time point, Moran's I and Geary's C of every gene with z-scores and p-values under the analytic
 (normality) null and under random relabelings of the spots: which genes are spatially structured inside a time point, how
 strongly, and with which sign (spadot_amd.autocorr).  `hotspots` reads the same counts and asks WHERE: local Moran's I
@@ -192,6 +195,13 @@ def build_parser():
                          "diagonal of the spots' bounding box.")
     co.add_argument("--ring", dest="ring", default=False, action="store_true",
                     help="Ratios of the pairs between consecutive radii (annuli) instead of within each radius (discs).")
+    co.add_argument("--n_perms", dest="n_perms", type=int, default=0,
+                    help="Random relabelings of the spots per time point, 0 to 9999: with 1 or more, the counts of every pair of "
+                         "domains are tested against them (envelope, p-values, a verdict attract / avoid / independent per "
+                         "pair). Default: 0, no test")
+    co.add_argument("--seed", dest="seed", type=int, default=0, help="Seed of the relabelings. Default: 0")
+    co.add_argument("--alpha", dest="alpha", type=float, default=0.05,
+                    help="Level of the adjusted global p-value below which a pair is called attract or avoid. Default: 0.05")
     co.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
 
     rp = sub.add_parser("ripley", help="Ripley's L, G and F of every spatial domain on its own, against a Monte-Carlo envelope: "

@@ -347,6 +347,60 @@ def cooccur_counts(xy, desc, r2, K_max, B_max, out=None):
     return cooccur_launch(xy, desc, pad, K_max, B_max, out)
 
 
+COOCCUR_DESC_G = 37                # the problem number g of the null: K <= 32 leaves the columns 37 .. 39 of a descriptor free
+COOCCUR_MAX_Y = 65535              # patterns of a call of the null (gridDim.y; its problems are gridDim.z)
+COOCCUR_MAX_G = 2147483647         # problem numbers, as the graph ids of spadot_nhood_counts
+COOCCUR_NULL_LIMITS = (COOCCUR_LIMITS + ", 1 to 65535 patterns per call, relabelings first >= 0 with first + n_perms <= 2^31, "
+                       "problem numbers in 0 .. 2147483647")
+
+
+def cooccur_null_check(xy, desc, r2, K_max, B_max, observed, first, n_perms):
+    """The refusals of cooccur_null_counts, before any launch: those of cooccur_check, the problem numbers in column 37 of the
+    descriptor and the patterns of the call.  Returns (desc, r2 padded, observed as 0 / 1, first, n_perms); ValueError
+    otherwise."""
+    desc, pad = cooccur_check(xy, desc, r2, K_max, B_max)
+    observed, first, n_perms = labelings("cooccur_null_counts", observed, first, n_perms)
+    if not 1 <= observed + n_perms <= COOCCUR_MAX_Y:
+        raise ValueError(f"the call holds {observed + n_perms} patterns: spadot_cooccur_null takes 1 to {COOCCUR_MAX_Y} (the grid "
+                         f"of one launch)")
+    if first + n_perms > 2 ** 31:
+        raise ValueError(f"relabelings {first} .. {first + n_perms - 1}: spadot_cooccur_null takes indices below 2^31")
+    for p, g in enumerate(desc[:, COOCCUR_DESC_G].tolist()):
+        if not 0 <= g <= COOCCUR_MAX_G:
+            raise ValueError(f"problem {p} has the problem number {g}: spadot_cooccur_null takes 0 to {COOCCUR_MAX_G}")
+    return desc, pad, observed, first, n_perms
+
+
+def cooccur_null_launch(xy, checked, K_max, B_max, seed=0, out=None, desc_dev=None, r2_dev=None):
+    """The launch of cooccur_null_counts for what cooccur_null_check has returned (the library checks it again, on the host)."""
+    desc, r2, observed, first, n_perms = checked
+    need_cuda(xy, out, desc_dev, r2_dev)
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    r2 = np.ascontiguousarray(r2, dtype=np.float64)
+    K_max, B_max, P, Y = int(K_max), int(B_max), int(desc.shape[0]), int(observed) + int(n_perms)
+    if out is None:
+        out = torch.empty((P, Y, K_max, K_max, B_max), dtype=torch.int64, device=xy.device)
+    elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != P * Y * K_max * K_max * B_max:
+        raise ValueError(f"out must be a contiguous int64 tensor of {P} x {Y} x {K_max} x {K_max} x {B_max} values")
+    if desc_dev is None:
+        desc_dev = torch.as_tensor(desc, device=xy.device)
+    if r2_dev is None:
+        r2_dev = torch.as_tensor(r2, device=xy.device)
+    launched(model_lib().spadot_cooccur_null(_p(xy), _host(desc), _p(desc_dev), _host(r2), _p(r2_dev), P, K_max, B_max,
+                                             int(observed), int(first), int(n_perms), _signed64(seed), _p(out), _stream()),
+             "spadot_cooccur_null", COOCCUR_NULL_LIMITS)
+    return out
+
+
+def cooccur_null_counts(xy, desc, r2, K_max, B_max, observed, first, n_perms, seed=0, out=None):
+    """The label-pair counts by distance of the observed labeling (observed) and of the relabelings first .. first + n_perms - 1
+    of many problems in ONE counting launch (include/spadot_model.h: spadot_cooccur_null).  xy, desc, r2 as for cooccur_counts,
+    with the problem number g of a problem in column 37 of its descriptor.  Returns int64 [P, observed + n_perms, K_max, K_max,
+    B_max] (out: the tensor to write into).  ValueError, before any launch, outside the limits."""
+    checked = cooccur_null_check(xy, desc, r2, K_max, B_max, observed, first, n_perms)
+    return cooccur_null_launch(xy, checked, K_max, B_max, seed, out)
+
+
 AUTOCORR_DESC = 7
 AUTOCORR_MAX = 2147483647          # spots, edges and stored entries (int32), graph ids, and workgroups of a call (gridDim.x)
 AUTOCORR_LDS_BYTES = 163840

@@ -230,6 +230,35 @@ def plot_cooccurrence(path, radii, ratio, timepoint, ring=False):
     fig.savefig(path)
 
 
+def plot_cooccurrence_null(path, radii, ratio, ratio_sim_min, ratio_sim_max, timepoint, ring=False, relation=None):
+    """{prefix}{tp}_cooccurrence_null.png: the curves of plot_cooccurrence, each over the envelope of its ratio under the
+    relabelings as a band of its own colour; a pair whose verdict is not 'independent' is drawn solid, the others dotted."""
+    import matplotlib
+    r = np.asarray(radii, dtype=np.float64)
+    v, lo, hi = (np.asarray(x, dtype=np.float64) for x in (ratio, ratio_sim_min, ratio_sim_max))
+    K = v.shape[0]
+    cols = min(K, 4)
+    rows = (K + cols - 1) // cols
+    fig = _figure((3.6 * cols + 1.2, 2.8 * rows + 0.6))
+    cmap = matplotlib.colormaps["tab20"]
+    for a in range(K):
+        ax = fig.add_subplot(rows, cols, a + 1)
+        for b in range(K):
+            found = relation is None or str(relation[a][b]) != "independent"
+            ax.fill_between(r, lo[a, b], hi[a, b], color=cmap(b % 20), alpha=0.2, linewidth=0)
+            ax.plot(r, v[a, b], color=cmap(b % 20), linewidth=2.0 if a == b else 1.0, linestyle="-" if found else ":",
+                    label=str(b))
+        ax.axhline(1.0, color="black", linewidth=0.8, linestyle="--")
+        ax.set_title("domain {}".format(a))
+        ax.set_xlabel("radius")
+        ax.set_ylabel("ratio")
+    handles, names = fig.axes[0].get_legend_handles_labels()
+    fig.legend(handles, names, title="neighbor", loc="center right")
+    fig.suptitle("Co-occurrence{} against random labelling, time point: {}".format(" (rings)" if ring else "", timepoint))
+    fig.tight_layout(rect=(0, 0, 1 - 1.0 / (3.6 * cols + 1.2), 0.96))
+    fig.savefig(path)
+
+
 def plot_ripley(path, radii, observed, sim_mean, sim_min, sim_max, timepoint, pattern=None):
     """{prefix}{tp}_ripley.png: one row per statistic (L, G, F), one panel per domain: the envelope of the simulations as a band,
     their mean dashed, the observed curve on top; a statistic that is not defined leaves its panel empty."""
