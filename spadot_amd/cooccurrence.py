@@ -50,15 +50,12 @@ import time
 
 import numpy as np
 
+from .pairs import MAX_BINS, NO_CPU, counted, default_radii, ladder, mad_p, sorted_problems, thresholds
+from .pairs import MAX_CLUSTERS, MAX_PROBLEMS, MAX_SPOTS  # noqa: F401  (handed on with the names above: tests and tools import them from here)
 from .utils._stage_utils import savez_pinned
 
-MAX_CLUSTERS = 32
-MAX_BINS = 64
-MAX_SPOTS = 2147483391
-MAX_PROBLEMS = 65535
 TABLE_COLUMNS = ("domain", "neighbor", "radius", "count", "ratio")
 ARRAYS = ("counts", "ratio", "radii", "sizes")
-NO_CPU = "spadot_amd counts co-occurrences on the MI355X only ({}); there is no CPU path"
 
 
 class CooccurResult:
@@ -88,124 +85,12 @@ def cooccurrence_stats(counts, ring=False):
     return dict(cond=cond, marg=marg, ratio=ratio)
 
 
-def _bounding_box(xy):
-    """(min x, max x, min y, max y) of an [n, 2] array or tensor as Python floats."""
-    if hasattr(xy, "is_cuda"):
-        import torch
-        if xy.dim() != 2 or xy.shape[1] != 2 or xy.shape[0] < 1:
-            raise ValueError(f"coords must be an [n, 2] array of at least one spot (got {tuple(xy.shape)})")
-        lo, hi = torch.aminmax(xy.to(torch.float64), dim=0)
-        lo, hi = lo.cpu().numpy(), hi.cpu().numpy()
-    else:
-        xy = np.asarray(xy, dtype=np.float64)
-        if xy.ndim != 2 or xy.shape[1] != 2 or xy.shape[0] < 1:
-            raise ValueError(f"coords must be an [n, 2] array of at least one spot (got {xy.shape})")
-        lo, hi = xy.min(axis=0), xy.max(axis=0)
-    return float(lo[0]), float(hi[0]), float(lo[1]), float(hi[1])
-
-
-def ladder(r_max, bins):
-    """The radii r_max * (1 .. bins) / bins."""
-    bins, r_max = int(bins), float(r_max)
-    if not 1 <= bins <= MAX_BINS:
-        raise ValueError(f"the co-occurrence takes 1 to {MAX_BINS} radii (got bins = {bins})")
-    if not np.isfinite(r_max) or r_max <= 0:
-        raise ValueError(f"the largest radius must be finite and above 0 (got {r_max})")
-    return r_max * np.arange(1, bins + 1) / bins
-
-
-def default_radii(coords, bins=50):
-    """The stage's radii of one time point: r_max = 0.25 * hypot(max x - min x, max y - min y), radii = r_max * (1 .. bins) /
-    bins.  ValueError where the spots all coincide (or are not finite)."""
-    x0, x1, y0, y1 = _bounding_box(coords)
-    r_max = 0.25 * np.hypot(x1 - x0, y1 - y0)
-    if not np.isfinite(r_max):
-        raise ValueError("the coordinates must be finite")
-    if r_max <= 0:
-        raise ValueError("the spots all coincide: there is no distance to bin (give radii)")
-    return ladder(r_max, bins)
-
-
-def _squares(radii, g):
-    r = np.asarray(radii, dtype=np.float64).reshape(-1)
-    if not 1 <= r.shape[0] <= MAX_BINS:
-        raise ValueError(f"problem {g} has {r.shape[0]} radii: the device takes 1 to {MAX_BINS}")
-    if not np.all(np.isfinite(r)) or np.any(r < 0) or np.any(np.diff(r) <= 0):
-        raise ValueError(f"the radii of problem {g} must be finite, >= 0 and strictly increasing")
-    return r * r
-
-
-def sorted_problems(coords, labels, n_clusters=None, no_cpu=NO_CPU):
-    """What the stages that count by distance refuse about the spots and the labelings of a call, before any launch, and the
-    layout they hand to the device.  Returns (the device, xy fp64 [sum n, 2] with every problem's spots ordered by (label,
-    index), [g] -> K, int64 [P, 32] domain sizes); one host round trip."""
-    import torch
-    P = len(coords)
-    dev, xs, labs = None, [], []
-    for g, (xy, lab) in enumerate(zip(coords, labels)):
-        if not isinstance(xy, torch.Tensor) or not xy.is_cuda:
-            raise RuntimeError(no_cpu.format("the coordinates of problem %d are not a device tensor" % g))
-        if xy.dim() != 2 or xy.shape[1] != 2 or xy.shape[0] < 1 or not xy.dtype.is_floating_point:
-            raise ValueError(f"the coordinates of problem {g} must form a floating-point [n, 2] block of at least one spot "
-                             f"(got {tuple(xy.shape)} {xy.dtype})")
-        if dev is not None and xy.device != dev:
-            raise ValueError("all problems of a call lie on one device")
-        dev = xy.device
-        if xy.shape[0] > MAX_SPOTS:
-            raise ValueError(f"problem {g} has {xy.shape[0]} spots: the device takes at most {MAX_SPOTS} per problem")
-        lab = lab if isinstance(lab, torch.Tensor) else torch.as_tensor(np.asarray(lab))
-        if lab.dtype.is_floating_point or lab.dtype == torch.bool or lab.dtype.is_complex:
-            raise ValueError(f"labels must be integers (problem {g}: {lab.dtype})")
-        if lab.dim() != 1 or lab.shape[0] != xy.shape[0]:
-            raise ValueError(f"problem {g} has {xy.shape[0]} spots and a labeling of shape {tuple(lab.shape)}")
-        xs.append(xy.to(torch.float64))
-        labs.append(lab.to(dev).long())
-    with torch.cuda.device(dev):
-        stats = []
-        for xy, lab in zip(xs, labs):
-            lo, hi = torch.aminmax(lab)
-            hist = torch.bincount(lab.clamp(0, MAX_CLUSTERS), minlength=MAX_CLUSTERS + 1)[:MAX_CLUSTERS]
-            stats.append(torch.cat([torch.stack([lo, hi, torch.isfinite(xy).all().long()]), hist]))
-        stats = torch.stack(stats).cpu().numpy()                       # the one host round trip ahead of the launch
-        Ks = []
-        for g in range(P):
-            lo, hi, finite = (int(v) for v in stats[g, :3])
-            K = hi + 1 if n_clusters is None else int(n_clusters[g])
-            if not 1 <= K <= MAX_CLUSTERS:
-                raise ValueError(f"problem {g} has {K} label values: the device counts 1 to {MAX_CLUSTERS} domains")
-            if lo < 0 or hi >= K:
-                raise ValueError(f"problem {g} holds labels {lo} .. {hi}: labels must lie in 0 .. {K - 1}")
-            if not finite:
-                raise ValueError(f"problem {g} holds coordinates that are not finite")
-            Ks.append(K)
-        # the spots of every problem by (label, index): a stable sort of the labels
-        xy = torch.cat([x[torch.sort(lab, stable=True)[1]] for x, lab in zip(xs, labs)]).contiguous()
-    return dev, xy, Ks, stats[:, 3:]
-
-
 def _layout(name, coords, labels, radii, radii_sq, n_clusters):
     """What cooccurrence_counts and cooccurrence_null_counts refuse about a call before any launch, and what they hand to the
     library: (the device, xy sorted by (label, index), [g] -> K, [g] -> squared thresholds, the descriptor int64 [P, 40])."""
     from . import stage_ops as ops
-    if (radii is None) == (radii_sq is None):
-        raise ValueError(f"{name} takes exactly one of radii and radii_sq")
-    given = radii if radii is not None else radii_sq
     P = len(coords)
-    if P < 1 or len(labels) != P or len(given) != P:
-        raise ValueError(f"{name} takes one labeling and one set of radii per problem ({P} problems, {len(labels)} "
-                         f"labelings, {len(given)} sets of radii)")
-    if n_clusters is not None and len(n_clusters) != P:
-        raise ValueError(f"n_clusters holds {len(n_clusters)} cluster counts for {P} problems")
-    if P > MAX_PROBLEMS:
-        raise ValueError(f"the call holds {P} problems: the device takes at most {MAX_PROBLEMS} per call")
-    r2 = []
-    for g, r in enumerate(given):
-        t = _squares(r, g) if radii is not None else np.asarray(r, dtype=np.float64).reshape(-1)
-        r2.append(t)                                     # two radii that differ may still have one square: checked as squares too
-        if not 1 <= t.shape[0] <= MAX_BINS:
-            raise ValueError(f"problem {g} has {t.shape[0]} thresholds: the device takes 1 to {MAX_BINS}")
-        if not np.all(np.isfinite(t)) or np.any(t < 0) or np.any(np.diff(t) <= 0):
-            raise ValueError(f"the squared thresholds of problem {g} must be finite, >= 0 and strictly increasing")
+    r2 = thresholds(name, P, radii, radii_sq, labelings=len(labels))
     dev, xy, Ks, sizes = sorted_problems(coords, labels, n_clusters)
     desc = np.zeros((P, ops.COOCCUR_DESC), dtype=np.int64)
     first = 0
@@ -234,19 +119,8 @@ def cooccurrence_counts(coords, labels, radii=None, radii_sq=None, n_clusters=No
 def cooccurrence(coords, labels, radii=None, bins=50, ring=False, n_clusters=None):
     """The co-occurrence of every problem (module docstring): coords[g] fp64 [n, 2] device tensors, labels[g] integers, radii[g]
     the radii of problem g (default: default_radii(coords[g], bins)).  One call to the library.  Returns [g] -> CooccurResult."""
-    import torch
-    for g, xy in enumerate(coords):
-        if not isinstance(xy, torch.Tensor) or not xy.is_cuda:
-            raise RuntimeError(NO_CPU.format("the coordinates of problem %d are not a device tensor" % g))
-    if radii is None:
-        radii = [default_radii(xy, bins) for xy in coords]
-    radii = [np.asarray(r, dtype=np.float64).reshape(-1) for r in radii]
-    counts = cooccurrence_counts(coords, labels, radii=radii, n_clusters=n_clusters)
-    out = []
-    for g, N in enumerate(counts):
-        lab = labels[g].cpu().numpy() if isinstance(labels[g], torch.Tensor) else np.asarray(labels[g])
-        out.append(CooccurResult(N, radii[g], np.bincount(lab, minlength=N.shape[0]).astype(np.int64), ring))
-    return out
+    return [CooccurResult(N, r, sizes, ring) for N, r, sizes in
+            counted(coords, labels, radii, bins, lambda r: cooccurrence_counts(coords, labels, radii=r, n_clusters=n_clusters))]
 
 
 def cooccurrence_null_counts(coords, labels, radii=None, radii_sq=None, n_perms=99, seed=0, n_clusters=None, problem_ids=None,
@@ -282,16 +156,6 @@ def cooccurrence_null_counts(coords, labels, radii=None, radii_sq=None, n_perms=
             first += count
     res = np.concatenate(parts, axis=1)
     return [np.ascontiguousarray(res[g, :, :Ks[g], :Ks[g], :r2[g].shape[0]]) for g in range(P)]
-
-
-def _mad_p(T):
-    """p_global of the integer curves T [1 + S, .., B] (module docstring), compared exactly: in int64 where (S + 1) max T cannot
-    wrap, with Python integers otherwise."""
-    n = T.shape[0]
-    if T.size and int(T.max()) * n >= 2 ** 62:
-        T = T.astype(object)
-    dev = np.abs(n * T - T.sum(axis=0, keepdims=True)).max(axis=-1)
-    return np.asarray((dev >= dev[:1]).sum(axis=0), dtype=np.float64) / n
 
 
 def cooccurrence_null_stats(N, sizes, ring=False, alpha=0.05):
@@ -330,7 +194,7 @@ def cooccurrence_null_stats(N, sizes, ring=False, alpha=0.05):
     with np.errstate(divide="ignore", invalid="ignore"):
         out.update(ratio=cooccurrence_stats(N[0], ring)["ratio"], ratio_sim_mean=np.where(cnt > 0, tot / cnt, np.nan),
                    ratio_sim_min=np.where(cnt > 0, lo, np.nan), ratio_sim_max=np.where(cnt > 0, hi, np.nan))
-    p_global = np.where(defined, _mad_p(T), np.nan)
+    p_global = np.where(defined, mad_p(T), np.nan)
     padj = np.full((K, K), np.nan)
     a, b = np.nonzero(np.triu(defined))                                   # N is symmetric: one test per unordered pair
     padj[a, b] = bh_adjust(p_global[a, b])
@@ -367,20 +231,10 @@ def cooccurrence_null(coords, labels, radii=None, bins=50, ring=False, n_perms=9
                       problem_ids=None, max_bytes=256 << 20):
     """The co-occurrence of every problem with its random-labelling null (module docstring): the arguments of cooccurrence and
     of cooccurrence_null_counts.  Returns [g] -> CooccurNullResult."""
-    import torch
-    for g, xy in enumerate(coords):
-        if not isinstance(xy, torch.Tensor) or not xy.is_cuda:
-            raise RuntimeError(NO_CPU.format("the coordinates of problem %d are not a device tensor" % g))
-    if radii is None:
-        radii = [default_radii(xy, bins) for xy in coords]
-    radii = [np.asarray(r, dtype=np.float64).reshape(-1) for r in radii]
-    counts = cooccurrence_null_counts(coords, labels, radii=radii, n_perms=n_perms, seed=seed, n_clusters=n_clusters,
-                                      problem_ids=problem_ids, max_bytes=max_bytes)
-    out = []
-    for g, N in enumerate(counts):
-        lab = labels[g].cpu().numpy() if isinstance(labels[g], torch.Tensor) else np.asarray(labels[g])
-        out.append(CooccurNullResult(N, radii[g], np.bincount(lab, minlength=N.shape[1]).astype(np.int64), ring, seed, alpha))
-    return out
+    def count(r):
+        return cooccurrence_null_counts(coords, labels, radii=r, n_perms=n_perms, seed=seed, n_clusters=n_clusters,
+                                        problem_ids=problem_ids, max_bytes=max_bytes)
+    return [CooccurNullResult(N, r, sizes, ring, seed, alpha) for N, r, sizes in counted(coords, labels, radii, bins, count, k_axis=1)]
 
 
 def cooccurrence_null_table(r):

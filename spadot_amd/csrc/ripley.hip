@@ -10,7 +10,7 @@
 //     Lc = #{ordered pairs i != j of the pattern : d2 <= r2[t]}
 //     Gc = #{points of the pattern whose nearest other point has d2 <= r2[t]}
 //     Fc = #{probe points (stream 0, shared by all patterns of the problem) whose nearest point of the pattern has d2 <= r2[t]}
-// with d2 the five rounded fp64 operations of cooccur.hip's co_d2 (rp_d2 below repeats them; no fused multiply-add).
+// with d2 the five rounded fp64 operations of pc_d2 (pair_count.h, shared with cooccur.hip; no fused multiply-add).
 //
 // rp_point        a generated point is a pure function of (seed, g, stream, i): three splitmix words at counter 3 i + j,
 //                 u_j = (w_j >> 11) 2^-53; the triangle is the first k with fl(u_0 cum[last]) < cum[k] (binary search, cum
@@ -30,29 +30,14 @@
 
 #include "../../include/spadot_model.h"
 #include "feistel_perm.h"
+#include "pair_count.h"
 
-#define RP_THREADS 256
-#define RP_MAX_K 32
-#define RP_MAX_B 64
-#define RP_GRANULE 16              // thresholds per problem are padded to a multiple of this
 #define RP_DESC 48                 // int64 columns of a problem's descriptor (include/spadot_model.h)
-#define RP_MAX_P 65535             // problems per launch: gridDim.z
-#define RP_MAX_Y 65535             // patterns per problem, K (1 + S): gridDim.y
-#define RP_MAX_N 2147483391        // spots per problem (CO_MAX_N of cooccur.hip)
 #define RP_MAX_S 9999
 #define RP_MAX_M 1048576
 #define RP_MAX_V 256
-#define RP_MAX_G 2147483647ll
 #define RP_GOLD 0x9E3779B97F4A7C15ull
 #define RP_SALT 0x52504C5953494D31ull                  // keeps the generator's keys apart from the Feistel round keys
-
-// the squared distance of the definition, as co_d2 of cooccur.hip: two multiplications and three additions, each rounded once
-__device__ __forceinline__ double rp_d2(double xi, double yi, double xj, double yj) {
-#pragma clang fp contract(off)
-    const double dx = xi - xj, dy = yi - yj;
-    const double sx = dx * dx, sy = dy * dy;
-    return sx + sy;
-}
 
 __host__ __device__ static inline unsigned long long rp_key(unsigned long long seed, unsigned long long g, unsigned long long stream) {
     unsigned long long s = seed ^ (g << 32) ^ stream;
@@ -86,11 +71,11 @@ __device__ __forceinline__ double2 rp_point(unsigned long long key, unsigned lon
 }
 
 template <int BP>
-__global__ void __launch_bounds__(RP_THREADS) k_ripley(const double2 *__restrict__ xy, const long long *__restrict__ desc,
+__global__ void __launch_bounds__(PC_THREADS) k_ripley(const double2 *__restrict__ xy, const long long *__restrict__ desc,
                                                         const double *__restrict__ r2, const double2 *__restrict__ hull,
                                                         const double *__restrict__ cum, unsigned long long seed, int K_max,
                                                         int S_max, int B_max, int qb_own, unsigned long long *__restrict__ out) {
-    __shared__ double2 tile[RP_THREADS];
+    __shared__ double2 tile[PC_THREADS];
     __shared__ double2 hv[RP_MAX_V];
     __shared__ double hc[RP_MAX_V];
     __shared__ unsigned long long tab[3 * BP];
@@ -98,7 +83,7 @@ __global__ void __launch_bounds__(RP_THREADS) k_ripley(const double2 *__restrict
     const long long *d = desc + (long long)p * RP_DESC;
     // the descriptor is refused on the host before the launch; the clamps keep every access inside its array
     const long long nl = d[1];
-    const int K = min(max((int)d[2], 1), min(K_max, RP_MAX_K));
+    const int K = min(max((int)d[2], 1), min(K_max, PC_MAX_K));
     const int B = min((int)d[3], min(B_max, BP));
     const int S = min(max((int)d[4], 1), S_max);
     const int M = (int)min(max(d[5], 1ll), (long long)RP_MAX_M);
@@ -109,15 +94,15 @@ __global__ void __launch_bounds__(RP_THREADS) k_ripley(const double2 *__restrict
     const int nc = hi - lo;
     if (nc == 0) return;                                 // a label value without spots: its counts stay zero
     const bool own = (int)blockIdx.x < qb_own;
-    const int q0 = ((int)blockIdx.x - (own ? 0 : qb_own)) * RP_THREADS;
+    const int q0 = ((int)blockIdx.x - (own ? 0 : qb_own)) * PC_THREADS;
     if (own ? ((modes & 3) == 0 || q0 >= nc) : ((modes & 4) == 0 || q0 >= M)) return;
 
     const int V = min(max((int)d[10], 3), RP_MAX_V), T = V - 2;
-    for (int i = tid; i < V; i += RP_THREADS) {
+    for (int i = tid; i < V; i += PC_THREADS) {
         hv[i] = hull[d[9] + i];
         hc[i] = cum[d[9] + i];
     }
-    for (int i = tid; i < 3 * BP; i += RP_THREADS) tab[i] = 0ull;
+    for (int i = tid; i < 3 * BP; i += PC_THREADS) tab[i] = 0ull;
     __syncthreads();
 
     const double2 *pts = xy + d[0];
@@ -146,46 +131,27 @@ __global__ void __launch_bounds__(RP_THREADS) k_ripley(const double2 *__restrict
 #pragma unroll
     for (int t = 0; t < BP; ++t) cnt[t] = 0;
 
-    for (int j0 = 0; j0 < nc; j0 += RP_THREADS) {
-        const int m = min(RP_THREADS, nc - j0);
+    for (int j0 = 0; j0 < nc; j0 += PC_THREADS) {
+        const int m = min(PC_THREADS, nc - j0);
         __syncthreads();                                 // the previous tile is read
         if (tid < m) tile[tid] = target(j0 + tid);
         __syncthreads();
         int jj = 0;
         if (doL) {
             for (; jj + 4 <= m; jj += 4) {               // four points per pass over the thresholds
-                double e[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const double2 v = tile[jj + u];
-                    const double sd = rp_d2(me.x, me.y, v.x, v.y);
-                    e[u] = j0 + jj + u == self ? INFINITY : sd;
-                }
-                mn = fmin(mn, fmin(fmin(e[0], e[1]), fmin(e[2], e[3])));
-#pragma unroll
-                for (int t = 0; t < BP; ++t) {
-                    const double r = th[t];
-                    cnt[t] += (int)(e[0] <= r) + (int)(e[1] <= r) + (int)(e[2] <= r) + (int)(e[3] <= r);
-                }
+                mn = fmin(mn, pc_pass4<BP>(cnt, th, me, tile + jj, j0 + jj, self));
             }
             for (; jj < m; ++jj) {
-                const double2 v = tile[jj];
-                const double sd = rp_d2(me.x, me.y, v.x, v.y);
-                const double e = j0 + jj == self ? INFINITY : sd;
+                const double e = pc_dist(me, tile[jj], j0 + jj, self);
                 mn = fmin(mn, e);
-#pragma unroll
-                for (int t = 0; t < BP; ++t) cnt[t] += (int)(e <= th[t]);
+                pc_count1<BP>(cnt, th, e);
             }
         } else {
-            for (; jj < m; ++jj) {                       // the nearest point alone
-                const double2 v = tile[jj];
-                const double sd = rp_d2(me.x, me.y, v.x, v.y);
-                mn = fmin(mn, j0 + jj == self ? INFINITY : sd);
-            }
+            for (; jj < m; ++jj) mn = fmin(mn, pc_dist(me, tile[jj], j0 + jj, self));     // the nearest point alone
         }
     }
     // the threads' counters into the table, the table onto the output
-    if (doL) {
+    if (doL) {                                           // written here: through pc_flush_counters BP = 16 changes its occupancy
 #pragma unroll
         for (int t = 0; t < BP; ++t)
             if (on && cnt[t] != 0) atomicAdd(&tab[t], (unsigned long long)cnt[t]);
@@ -198,25 +164,20 @@ __global__ void __launch_bounds__(RP_THREADS) k_ripley(const double2 *__restrict
         }
     }
     __syncthreads();
-    for (int i = tid; i < 3 * BP; i += RP_THREADS) {
-        const unsigned long long v = tab[i];
-        const int stat = i / BP, t = i - stat * BP;
-        if (v != 0ull && t < B)
-            atomicAdd(out + (((((long long)p * K_max + c) * (1 + S_max) + s) * 3 + stat) * B_max + t), v);
-    }
+    pc_flush_table<BP>(tab, 3, B, out + ((((long long)p * K_max + c) * (1 + S_max) + s) * 3) * B_max, B_max);
 }
 
-__global__ void __launch_bounds__(RP_THREADS) k_ripley_points(const double2 *__restrict__ hull, const double *__restrict__ cum, int V,
+__global__ void __launch_bounds__(PC_THREADS) k_ripley_points(const double2 *__restrict__ hull, const double *__restrict__ cum, int V,
                                                                unsigned long long key, long long count, double2 *__restrict__ out) {
     __shared__ double2 hv[RP_MAX_V];
     __shared__ double hc[RP_MAX_V];
     V = min(max(V, 3), RP_MAX_V);
-    for (int i = threadIdx.x; i < V; i += RP_THREADS) {
+    for (int i = threadIdx.x; i < V; i += PC_THREADS) {
         hv[i] = hull[i];
         hc[i] = i < V - 2 ? cum[i] : 0.0;
     }
     __syncthreads();
-    const long long i = (long long)blockIdx.x * RP_THREADS + threadIdx.x;
+    const long long i = (long long)blockIdx.x * PC_THREADS + threadIdx.x;
     if (i < count) out[i] = rp_point(key, (unsigned long long)i, hv, hc, V - 2);
 }
 
@@ -244,15 +205,6 @@ static int rp_window(const double *h, const double *c, long long V) {
     return 0;
 }
 
-template <int BP>
-static int rp_launch(dim3 grid, hipStream_t st, const double *xy, const long long *desc, const double *r2, const double *hull,
-                     const double *cum, unsigned long long seed, int K_max, int S_max, int B_max, int qb_own, long long *out) {
-    hipLaunchKernelGGL(k_ripley<BP>, grid, dim3(RP_THREADS), 0, st, reinterpret_cast<const double2 *>(xy), desc, r2,
-                       reinterpret_cast<const double2 *>(hull), cum, seed, K_max, S_max, B_max, qb_own,
-                       reinterpret_cast<unsigned long long *>(out));
-    return hipGetLastError() == hipSuccess ? 0 : -5;
-}
-
 extern "C" int spadot_ripley_counts(const double *xy, const long long *desc_host, const long long *desc_dev,
                                     const double *r2_host, const double *r2_dev, const double *hull_host,
                                     const double *hull_dev, const double *cum_host, const double *cum_dev, long long hull_rows,
@@ -260,61 +212,52 @@ extern "C" int spadot_ripley_counts(const double *xy, const long long *desc_host
     if (!xy || !desc_host || !desc_dev || !r2_host || !r2_dev || !hull_host || !hull_dev || !cum_host || !cum_dev || !out ||
         P <= 0 || hull_rows < 3)
         return -22;
-    if (K_max < 1 || K_max > RP_MAX_K || B_max < 1 || B_max > RP_MAX_B || S_max < 1 || S_max > RP_MAX_S || P > RP_MAX_P)
+    if (K_max < 1 || K_max > PC_MAX_K || B_max < 1 || B_max > PC_MAX_B || S_max < 1 || S_max > RP_MAX_S || P > PC_MAX_GRID)
         return -7;
-    const int BP = (B_max + RP_GRANULE - 1) / RP_GRANULE * RP_GRANULE;
+    const int BP = pc_padded(B_max);
     long long first = 0, nc_max = 0, m_max = 0, y_max = 0;
     for (int p = 0; p < P; ++p) {
         const long long *d = desc_host + (long long)p * RP_DESC;
         const long long n = d[1], K = d[2], B = d[3], S = d[4], M = d[5], V = d[10];
         if (n < 1 || d[0] != first) return -22;          // the problems lie back to back in xy
-        if (n > RP_MAX_N || K < 1 || K > K_max || B < 1 || B > B_max || S < 1 || S > S_max || M < 1 || M > RP_MAX_M ||
-            K * (1 + S) > RP_MAX_Y || V > RP_MAX_V)
+        if (n > PC_MAX_N || K < 1 || K > K_max || B < 1 || B > B_max || S < 1 || S > S_max || M < 1 || M > RP_MAX_M ||
+            K * (1 + S) > PC_MAX_GRID || V > RP_MAX_V)
             return -7;
-        if ((d[6] != 0 && d[6] != 1) || d[7] < 1 || d[7] > 7 || d[8] < 0 || d[8] > RP_MAX_G) return -22;
+        if ((d[6] != 0 && d[6] != 1) || d[7] < 1 || d[7] > 7 || d[8] < 0 || d[8] > PC_MAX_G) return -22;
         if (V < 3 || d[9] < 0 || d[9] + V > hull_rows) return -22;
-        if (d[12] != 0 || d[12 + K] != n) return -22;
-        for (int k = 0; k < K; ++k) {
-            if (d[13 + k] < d[12 + k]) return -22;
-            if ((d[7] & 3) && d[13 + k] - d[12 + k] > nc_max) nc_max = d[13 + k] - d[12 + k];
-        }
-        const int rc = rp_window(hull_host + 2 * d[9], cum_host + d[9], V);
+        int rc = pc_offsets(d + 12, K, n);
+        if (!rc) rc = rp_window(hull_host + 2 * d[9], cum_host + d[9], V);
+        if (!rc) rc = pc_thresholds(r2_host + (long long)p * BP, B, BP);
         if (rc) return rc;
-        const double *r = r2_host + (long long)p * BP;
-        for (int t = 0; t < BP; ++t) {
-            if (t >= B) {
-                if (r[t] != -1.0) return -22;            // the padding
-            } else if (!std::isfinite(r[t]) || r[t] < 0.0 || (t > 0 && !(r[t] > r[t - 1]))) {
-                return -7;
-            }
-        }
+        for (int k = 0; k < K; ++k)                       // the largest domain that queries its own points
+            if ((d[7] & 3) && d[13 + k] - d[12 + k] > nc_max) nc_max = d[13 + k] - d[12 + k];
         first += n;
         if ((d[7] & 4) && M > m_max) m_max = M;
         if (K * (1 + S) > y_max) y_max = K * (1 + S);
     }
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(out, 0, sizeof(long long) * (size_t)P * K_max * (1 + S_max) * 3 * B_max, st) != hipSuccess) return -5;
-    const int qb_own = (int)((nc_max + RP_THREADS - 1) / RP_THREADS), qb_probe = (int)((m_max + RP_THREADS - 1) / RP_THREADS);
+    const int qb_own = (int)((nc_max + PC_THREADS - 1) / PC_THREADS), qb_probe = (int)((m_max + PC_THREADS - 1) / PC_THREADS);
     const dim3 grid((unsigned)(qb_own + qb_probe), (unsigned)y_max, (unsigned)P);
     const unsigned long long sd = (unsigned long long)seed;
-    switch (BP) {
-        case 16: return rp_launch<16>(grid, st, xy, desc_dev, r2_dev, hull_dev, cum_dev, sd, K_max, S_max, B_max, qb_own, out);
-        case 32: return rp_launch<32>(grid, st, xy, desc_dev, r2_dev, hull_dev, cum_dev, sd, K_max, S_max, B_max, qb_own, out);
-        case 48: return rp_launch<48>(grid, st, xy, desc_dev, r2_dev, hull_dev, cum_dev, sd, K_max, S_max, B_max, qb_own, out);
-        default: return rp_launch<64>(grid, st, xy, desc_dev, r2_dev, hull_dev, cum_dev, sd, K_max, S_max, B_max, qb_own, out);
-    }
+    return pc_dispatch(BP, [&](auto bp) {
+        hipLaunchKernelGGL(k_ripley<decltype(bp)::value>, grid, dim3(PC_THREADS), 0, st, reinterpret_cast<const double2 *>(xy),
+                           desc_dev, r2_dev, reinterpret_cast<const double2 *>(hull_dev), cum_dev, sd, K_max, S_max, B_max, qb_own,
+                           reinterpret_cast<unsigned long long *>(out));
+        return hipGetLastError() == hipSuccess ? 0 : -5;
+    });
 }
 
 extern "C" int spadot_ripley_points(const double *hull_host, const double *hull_dev, const double *cum_host, const double *cum_dev,
                                     int V, long long seed, long long g, long long stream_id, long long count, double *out,
                                     void *stream) {
     if (!hull_host || !hull_dev || !cum_host || !cum_dev || !out) return -22;
-    if (count < 1 || count > RP_MAX_N || stream_id < 0 || stream_id > 1ll + (long long)RP_MAX_K * RP_MAX_S) return -7;
-    if (g < 0 || g > RP_MAX_G) return -22;
+    if (count < 1 || count > PC_MAX_N || stream_id < 0 || stream_id > 1ll + (long long)PC_MAX_K * RP_MAX_S) return -7;
+    if (g < 0 || g > PC_MAX_G) return -22;
     const int rc = rp_window(hull_host, cum_host, V);
     if (rc) return rc;
     const unsigned long long key = rp_key((unsigned long long)seed, (unsigned long long)g, (unsigned long long)stream_id);
-    hipLaunchKernelGGL(k_ripley_points, dim3((unsigned)((count + RP_THREADS - 1) / RP_THREADS)), dim3(RP_THREADS), 0,
+    hipLaunchKernelGGL(k_ripley_points, dim3((unsigned)((count + PC_THREADS - 1) / PC_THREADS)), dim3(PC_THREADS), 0,
                        (hipStream_t)stream, reinterpret_cast<const double2 *>(hull_dev), cum_dev, V, key, count,
                        reinterpret_cast<double2 *>(out));
     return hipGetLastError() == hipSuccess ? 0 : -5;

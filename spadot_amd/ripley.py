@@ -55,7 +55,7 @@ import time
 
 import numpy as np
 
-from .cooccurrence import MAX_BINS, MAX_PROBLEMS, _squares, default_radii, ladder
+from .pairs import MAX_BINS, counted, default_radii, ladder, mad_p, sorted_problems, thresholds
 from .utils._stage_utils import savez_pinned
 
 MAX_SIMULATIONS = 9999
@@ -187,18 +187,8 @@ def ripley_counts(coords, labels, radii=None, radii_sq=None, n_sim=99, n_probes=
     [P, K_max, 1 + S_max, 3, B_max] to write into; windows_out: a list that receives every problem's Window."""
     import torch
     from . import stage_ops as ops
-    from .cooccurrence import sorted_problems
-    if (radii is None) == (radii_sq is None):
-        raise ValueError("ripley_counts takes exactly one of radii and radii_sq")
-    given = radii if radii is not None else radii_sq
     P = len(coords)
-    if P < 1 or len(labels) != P or len(given) != P:
-        raise ValueError(f"ripley_counts takes one labeling and one set of radii per problem ({P} problems, {len(labels)} "
-                         f"labelings, {len(given)} sets of radii)")
-    if n_clusters is not None and len(n_clusters) != P:
-        raise ValueError(f"n_clusters holds {len(n_clusters)} cluster counts for {P} problems")
-    if P > MAX_PROBLEMS:
-        raise ValueError(f"the call holds {P} problems: the device takes at most {MAX_PROBLEMS} per call")
+    r2 = thresholds("ripley_counts", P, radii, radii_sq, labelings=len(labels))
     S = [int(v) for v in _per(n_sim, P, "n_sim")]
     M = [int(v) for v in _per(n_probes, P, "n_probes")]
     nulls = _per(null, P, "null")
@@ -206,14 +196,7 @@ def ripley_counts(coords, labels, radii=None, radii_sq=None, n_sim=99, n_probes=
     gids = list(range(P)) if problem_ids is None else [int(v) for v in problem_ids]
     if len(gids) != P or any(not 0 <= v <= ops.RIPLEY_MAX_G for v in gids):
         raise ValueError(f"problem_ids holds one number in 0 .. {ops.RIPLEY_MAX_G} per problem")
-    r2 = []
-    for g, r in enumerate(given):
-        t = _squares(r, g) if radii is not None else np.asarray(r, dtype=np.float64).reshape(-1)
-        r2.append(t)
-        if not 1 <= t.shape[0] <= MAX_BINS:
-            raise ValueError(f"problem {g} has {t.shape[0]} thresholds: the device takes 1 to {MAX_BINS}")
-        if not np.all(np.isfinite(t)) or np.any(t < 0) or np.any(np.diff(t) <= 0):
-            raise ValueError(f"the squared thresholds of problem {g} must be finite, >= 0 and strictly increasing")
+    for g in range(P):
         if not 1 <= S[g] <= MAX_SIMULATIONS:
             raise ValueError(f"problem {g} asks for {S[g]} simulations: the device takes 1 to {MAX_SIMULATIONS}")
         if not 1 <= M[g] <= MAX_PROBES:
@@ -248,16 +231,6 @@ def ripley_points(window, seed=0, g=0, stream=0, count=1000, device="cuda:0"):
     return ops.ripley_points(w.vertices, w.cum, seed, g, stream, count, device=device)
 
 
-def _mad_p(x, exact):
-    """p_global of the curves x [.., 1 + S, B] (module docstring); exact: integers are compared as integers."""
-    n = x.shape[-2]
-    if exact:
-        dev = np.abs(n * x.astype(np.int64) - x.astype(np.int64).sum(axis=-2, keepdims=True)).max(axis=-1)
-    else:
-        dev = np.abs(n * x - x.sum(axis=-2, keepdims=True)).max(axis=-1)
-    return (dev >= dev[..., :1]).sum(axis=-1) / float(n)
-
-
 def ripley_stats(counts, sizes, area, n_probes, alpha=0.05, modes=STATS):
     """The host statistics of one problem from its integers (module docstring).  counts int64 [K, 1 + S, 3, B]; sizes [K]; area,
     n_probes: the window's area and M; modes: the statistics that were counted.  Returns a dict: value fp64 [3, K, 1 + S, B] (L,
@@ -289,9 +262,9 @@ def ripley_stats(counts, sizes, area, n_probes, alpha=0.05, modes=STATS):
         p_hi = np.where(defined[:, :, None], (1 + (Ni[:, :, 1:] >= Ni[:, :, :1]).sum(axis=2)) / (S + 1.0), np.nan)
         p_lo = np.where(defined[:, :, None], (1 + (Ni[:, :, 1:] <= Ni[:, :, :1]).sum(axis=2)) / (S + 1.0), np.nan)
     p_global = np.full((3, K), np.nan)
-    p_global[0, defined[0]] = _mad_p(value[0, defined[0]], exact=False)
-    p_global[1, defined[1]] = _mad_p(Ni[1, defined[1]], exact=True)
-    p_global[2, defined[2]] = _mad_p(Ni[2, defined[2]], exact=True)
+    p_global[0, defined[0]] = mad_p(value[0, defined[0]], axis=-2)        # L in fp64, G and F on the integers
+    p_global[1, defined[1]] = mad_p(Ni[1, defined[1]], axis=-2)
+    p_global[2, defined[2]] = mad_p(Ni[2, defined[2]], axis=-2)
     padj = np.full((3, K), np.nan)
     for i in range(3):
         padj[i, defined[i]] = bh_adjust(p_global[i, defined[i]])
@@ -321,24 +294,16 @@ def ripley(coords, labels, radii=None, bins=50, n_sim=99, n_probes=1000, null="l
     """Ripley's L, G and F of every domain of every problem (module docstring): coords[g] fp64 [n, 2] device tensors, labels[g]
     integers, radii[g] the radii of problem g (default: default_radii(coords[g], bins)).  One call to the library.  Returns
     [g] -> RipleyResult."""
-    import torch
-    for g, xy in enumerate(coords):
-        if not isinstance(xy, torch.Tensor) or not xy.is_cuda:
-            raise RuntimeError(NO_CPU.format("the coordinates of problem %d are not a device tensor" % g))
-    if radii is None:
-        radii = [default_radii(xy, bins) for xy in coords]
-    radii = [np.asarray(r, dtype=np.float64).reshape(-1) for r in radii]
     wins = []
-    counts = ripley_counts(coords, labels, radii=radii, n_sim=n_sim, n_probes=n_probes, null=null, modes=modes, seed=seed,
-                           window=window, n_clusters=n_clusters, problem_ids=problem_ids, windows_out=wins)
+
+    def count(r):
+        return ripley_counts(coords, labels, radii=r, n_sim=n_sim, n_probes=n_probes, null=null, modes=modes, seed=seed,
+                             window=window, n_clusters=n_clusters, problem_ids=problem_ids, windows_out=wins)
+    res = counted(coords, labels, radii, bins, count, no_cpu=NO_CPU)
     P = len(coords)
     M, nulls, masks = _per(n_probes, P, "n_probes"), _per(null, P, "null"), _per(modes, P, "modes")
-    out = []
-    for g, N in enumerate(counts):
-        lab = labels[g].cpu().numpy() if isinstance(labels[g], torch.Tensor) else np.asarray(labels[g])
-        out.append(RipleyResult(N, radii[g], np.bincount(lab, minlength=N.shape[0]).astype(np.int64), wins[g].vertices,
-                                wins[g].area, M[g], nulls[g], seed, alpha, masks[g]))
-    return out
+    return [RipleyResult(N, r, sizes, wins[g].vertices, wins[g].area, M[g], nulls[g], seed, alpha, masks[g])
+            for g, (N, r, sizes) in enumerate(res)]
 
 
 def ripley_table(r):

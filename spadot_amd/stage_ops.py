@@ -266,11 +266,43 @@ COOCCUR_MAX_P = 65535              # problems of a call (gridDim.y)
 COOCCUR_DESC = 40
 COOCCUR_LIMITS = ("1 <= K <= 32 label values, 1 <= B <= 64 thresholds that are finite, >= 0 and strictly increasing, "
                   "1 <= n <= 2147483391 spots per problem, at most 65535 problems per call")
+COOCCUR_DESC_G = 37                # the problem number g of the null: K <= 32 leaves the columns 37 .. 39 of a descriptor free
+COOCCUR_MAX_Y = 65535              # patterns of a call of the null (gridDim.y; its problems are gridDim.z)
+COOCCUR_MAX_G = 2147483647         # problem numbers, as the graph ids of spadot_nhood_counts
+COOCCUR_NULL_LIMITS = (COOCCUR_LIMITS + ", 1 to 65535 patterns per call, relabelings first >= 0 with first + n_perms <= 2^31, "
+                       "problem numbers in 0 .. 2147483647")
 
 
 def cooccur_padded(B_max):
     """The threshold columns of a call whose largest problem has B_max thresholds."""
     return (int(B_max) + COOCCUR_GRANULE - 1) // COOCCUR_GRANULE * COOCCUR_GRANULE
+
+
+def _cluster_offsets_ok(coff, n):
+    """The cluster-offset rule of the stages that count pairs by distance: a problem's K + 1 offsets ascend from 0 to n."""
+    return coff[0] == 0 and coff[-1] == n and all(hi >= lo for lo, hi in zip(coff, coff[1:]))
+
+
+def _padded_thresholds(pad, p, t, B):
+    """Writes the B squared thresholds t of problem p, given as they are or already padded to pad's width with -1.0, into row p
+    of pad (fp64 [P, BP], filled with -1.0); ValueError unless they are B finite values >= 0 in strictly increasing order."""
+    t = np.asarray(t, dtype=np.float64).reshape(-1)
+    if t.shape[0] == pad.shape[1] and np.all(t[B:] == -1.0):
+        t = t[:B]
+    if t.shape[0] != B:
+        raise ValueError(f"problem {p} has {t.shape[0]} thresholds and its descriptor says {B}")
+    if not np.all(np.isfinite(t)) or np.any(t < 0) or np.any(np.diff(t) <= 0):
+        raise ValueError(f"the squared thresholds of problem {p} must be finite, >= 0 and strictly increasing")
+    pad[p, :B] = t
+
+
+def _out_int64(out, shape, device):
+    """The int64 output of a counting launch: a fresh tensor of `shape`, or the caller's if it is contiguous and of that size."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.int64, device=device)
+    if out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != int(np.prod(shape, dtype=object)):
+        raise ValueError(f"out must be a contiguous int64 tensor of {' x '.join(str(v) for v in shape)} values")
+    return out
 
 
 def cooccur_check(xy, desc, r2, K_max, B_max):
@@ -289,8 +321,7 @@ def cooccur_check(xy, desc, r2, K_max, B_max):
                          f"launch)")
     if len(r2) != P:
         raise ValueError(f"the call holds {P} problems and {len(r2)} sets of thresholds")
-    BP = cooccur_padded(B_max)
-    pad = np.full((P, BP), -1.0, dtype=np.float64)
+    pad = np.full((P, cooccur_padded(B_max)), -1.0, dtype=np.float64)
     first = 0
     for p, row in enumerate(desc.tolist()):
         off, n, K, B = row[:4]
@@ -302,40 +333,39 @@ def cooccur_check(xy, desc, r2, K_max, B_max):
                              f"{COOCCUR_MAX_B}")
         if not 1 <= n <= COOCCUR_MAX_N:
             raise ValueError(f"problem {p} has {n} spots: spadot_cooccur_counts takes 1 to {COOCCUR_MAX_N} (int32 positions)")
-        coff = row[4:5 + K]
-        if off != first or coff[0] != 0 or coff[-1] != n or any(hi < lo for lo, hi in zip(coff, coff[1:])):
+        if off != first or not _cluster_offsets_ok(row[4:5 + K], n):
             raise ValueError(f"problem {p}: inconsistent descriptor {row[:5 + K]}")
         first += n
-        t = np.asarray(r2[p], dtype=np.float64).reshape(-1)
-        if t.shape[0] == BP and np.all(t[B:] == -1.0):
-            t = t[:B]
-        if t.shape[0] != B:
-            raise ValueError(f"problem {p} has {t.shape[0]} thresholds and its descriptor says {B}")
-        if not np.all(np.isfinite(t)) or np.any(t < 0) or np.any(np.diff(t) <= 0):
-            raise ValueError(f"the squared thresholds of problem {p} must be finite, >= 0 and strictly increasing")
-        pad[p, :B] = t
+        _padded_thresholds(pad, p, r2[p], B)
     if xy.dtype != torch.float64 or xy.dim() != 2 or xy.shape[1] != 2 or not xy.is_contiguous() or xy.shape[0] != first:
         raise ValueError(f"xy must be a contiguous fp64 [{first}, 2] tensor (got {tuple(xy.shape)} {xy.dtype})")
     return desc, pad
 
 
-def cooccur_launch(xy, desc, r2, K_max, B_max, out=None, desc_dev=None, r2_dev=None):
-    """The launch of cooccur_counts for what cooccur_check has returned (the library checks both again, on the host)."""
+def _cooccur_launch(xy, desc, r2, K_max, B_max, null, out, desc_dev, r2_dev):
+    """The launch of both entries.  null: None for spadot_cooccur_counts, (observed, first, n_perms, seed) for spadot_cooccur_null."""
     need_cuda(xy, out, desc_dev, r2_dev)
     desc = np.ascontiguousarray(desc, dtype=np.int64)
     r2 = np.ascontiguousarray(r2, dtype=np.float64)
     K_max, B_max, P = int(K_max), int(B_max), int(desc.shape[0])
-    if out is None:
-        out = torch.empty((P, K_max, K_max, B_max), dtype=torch.int64, device=xy.device)
-    elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != P * K_max * K_max * B_max:
-        raise ValueError(f"out must be a contiguous int64 tensor of {P} x {K_max} x {K_max} x {B_max} values")
+    out = _out_int64(out, (P,) + (() if null is None else (int(null[0]) + int(null[2]),)) + (K_max, K_max, B_max), xy.device)
     if desc_dev is None:
         desc_dev = torch.as_tensor(desc, device=xy.device)
     if r2_dev is None:
         r2_dev = torch.as_tensor(r2, device=xy.device)
-    launched(model_lib().spadot_cooccur_counts(_p(xy), _host(desc), _p(desc_dev), _host(r2), _p(r2_dev), P, K_max, B_max, _p(out),
-                                               _stream()), "spadot_cooccur_counts", COOCCUR_LIMITS)
+    args = (_p(xy), _host(desc), _p(desc_dev), _host(r2), _p(r2_dev), P, K_max, B_max)
+    if null is None:
+        launched(model_lib().spadot_cooccur_counts(*args, _p(out), _stream()), "spadot_cooccur_counts", COOCCUR_LIMITS)
+    else:
+        observed, first, n_perms, seed = null
+        launched(model_lib().spadot_cooccur_null(*args, int(observed), int(first), int(n_perms), _signed64(seed), _p(out),
+                                                 _stream()), "spadot_cooccur_null", COOCCUR_NULL_LIMITS)
     return out
+
+
+def cooccur_launch(xy, desc, r2, K_max, B_max, out=None, desc_dev=None, r2_dev=None):
+    """The launch of cooccur_counts for what cooccur_check has returned (the library checks both again, on the host)."""
+    return _cooccur_launch(xy, desc, r2, K_max, B_max, None, out, desc_dev, r2_dev)
 
 
 def cooccur_counts(xy, desc, r2, K_max, B_max, out=None):
@@ -345,13 +375,6 @@ def cooccur_counts(xy, desc, r2, K_max, B_max, out=None):
     [P, K_max, K_max, B_max] (out: the tensor to write into).  ValueError, before any launch, outside the limits."""
     desc, pad = cooccur_check(xy, desc, r2, K_max, B_max)
     return cooccur_launch(xy, desc, pad, K_max, B_max, out)
-
-
-COOCCUR_DESC_G = 37                # the problem number g of the null: K <= 32 leaves the columns 37 .. 39 of a descriptor free
-COOCCUR_MAX_Y = 65535              # patterns of a call of the null (gridDim.y; its problems are gridDim.z)
-COOCCUR_MAX_G = 2147483647         # problem numbers, as the graph ids of spadot_nhood_counts
-COOCCUR_NULL_LIMITS = (COOCCUR_LIMITS + ", 1 to 65535 patterns per call, relabelings first >= 0 with first + n_perms <= 2^31, "
-                       "problem numbers in 0 .. 2147483647")
 
 
 def cooccur_null_check(xy, desc, r2, K_max, B_max, observed, first, n_perms):
@@ -374,22 +397,7 @@ def cooccur_null_check(xy, desc, r2, K_max, B_max, observed, first, n_perms):
 def cooccur_null_launch(xy, checked, K_max, B_max, seed=0, out=None, desc_dev=None, r2_dev=None):
     """The launch of cooccur_null_counts for what cooccur_null_check has returned (the library checks it again, on the host)."""
     desc, r2, observed, first, n_perms = checked
-    need_cuda(xy, out, desc_dev, r2_dev)
-    desc = np.ascontiguousarray(desc, dtype=np.int64)
-    r2 = np.ascontiguousarray(r2, dtype=np.float64)
-    K_max, B_max, P, Y = int(K_max), int(B_max), int(desc.shape[0]), int(observed) + int(n_perms)
-    if out is None:
-        out = torch.empty((P, Y, K_max, K_max, B_max), dtype=torch.int64, device=xy.device)
-    elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != P * Y * K_max * K_max * B_max:
-        raise ValueError(f"out must be a contiguous int64 tensor of {P} x {Y} x {K_max} x {K_max} x {B_max} values")
-    if desc_dev is None:
-        desc_dev = torch.as_tensor(desc, device=xy.device)
-    if r2_dev is None:
-        r2_dev = torch.as_tensor(r2, device=xy.device)
-    launched(model_lib().spadot_cooccur_null(_p(xy), _host(desc), _p(desc_dev), _host(r2), _p(r2_dev), P, K_max, B_max,
-                                             int(observed), int(first), int(n_perms), _signed64(seed), _p(out), _stream()),
-             "spadot_cooccur_null", COOCCUR_NULL_LIMITS)
-    return out
+    return _cooccur_launch(xy, desc, r2, K_max, B_max, (observed, first, n_perms, seed), out, desc_dev, r2_dev)
 
 
 def cooccur_null_counts(xy, desc, r2, K_max, B_max, observed, first, n_perms, seed=0, out=None):
@@ -923,15 +931,15 @@ def cross_sums(Z, Y, desc, ng, observed, first, P, seed=0, out=None):
     return cross_launch(Z, Y, cross_check(Z, Y, desc, ng, observed, first, P), ng, observed, first, P, seed, out)
 
 
-RIPLEY_MAX_K = 32
-RIPLEY_MAX_B = 64
+RIPLEY_MAX_K = COOCCUR_MAX_K
+RIPLEY_MAX_B = COOCCUR_MAX_B
 RIPLEY_MAX_S = 9999                # simulations of a problem
 RIPLEY_MAX_M = 1048576             # probe points of a problem
 RIPLEY_MAX_V = 256                 # vertices of a window (LDS)
 RIPLEY_MAX_N = COOCCUR_MAX_N
-RIPLEY_MAX_P = 65535               # problems of a call (gridDim.z)
-RIPLEY_MAX_Y = 65535               # patterns of a problem, K (1 + S) (gridDim.y)
-RIPLEY_MAX_G = 2147483647          # problem numbers, as the graph ids of spadot_nhood_counts
+RIPLEY_MAX_P = COOCCUR_MAX_P       # problems of a call (gridDim.z)
+RIPLEY_MAX_Y = COOCCUR_MAX_Y       # patterns of a problem, K (1 + S) (gridDim.y)
+RIPLEY_MAX_G = COOCCUR_MAX_G       # problem numbers, as the graph ids of spadot_nhood_counts
 RIPLEY_MAX_STREAM = 1 + RIPLEY_MAX_K * RIPLEY_MAX_S
 RIPLEY_DESC = 48
 RIPLEY_MODES = {"L": 1, "G": 2, "F": 4}
@@ -981,8 +989,7 @@ def ripley_check(xy, desc, r2, windows, K_max, S_max, B_max):
         raise ValueError(f"the call holds {P} problems: spadot_ripley_counts takes at most {RIPLEY_MAX_P} (the grid of one launch)")
     if len(r2) != P or len(windows) != P:
         raise ValueError(f"the call holds {P} problems, {len(r2)} sets of thresholds and {len(windows)} windows")
-    BP = cooccur_padded(B_max)
-    pad = np.full((P, BP), -1.0, dtype=np.float64)
+    pad = np.full((P, cooccur_padded(B_max)), -1.0, dtype=np.float64)
     first, rows, hulls, cums = 0, 0, [], []
     for p, row in enumerate(desc.tolist()):
         off, n, K, B, S, M, null, modes, g = row[:9]
@@ -999,19 +1006,11 @@ def ripley_check(xy, desc, r2, windows, K_max, S_max, B_max):
         if K * (1 + S) > RIPLEY_MAX_Y:
             raise ValueError(f"problem {p} has {K} x {1 + S} patterns: spadot_ripley_counts takes at most {RIPLEY_MAX_Y} per problem "
                              f"(the grid of one launch)")
-        coff = row[12:13 + K]
-        if (off != first or coff[0] != 0 or coff[-1] != n or any(hi < lo for lo, hi in zip(coff, coff[1:])) or null not in (0, 1)
-                or not 1 <= modes <= 7 or not 0 <= g <= RIPLEY_MAX_G):
+        if (off != first or not _cluster_offsets_ok(row[12:13 + K], n) or null not in (0, 1) or not 1 <= modes <= 7
+                or not 0 <= g <= RIPLEY_MAX_G):
             raise ValueError(f"problem {p}: inconsistent descriptor {row[:13 + K]}")
         first += n
-        t = np.asarray(r2[p], dtype=np.float64).reshape(-1)
-        if t.shape[0] == BP and np.all(t[B:] == -1.0):
-            t = t[:B]
-        if t.shape[0] != B:
-            raise ValueError(f"problem {p} has {t.shape[0]} thresholds and its descriptor says {B}")
-        if not np.all(np.isfinite(t)) or np.any(t < 0) or np.any(np.diff(t) <= 0):
-            raise ValueError(f"the squared thresholds of problem {p} must be finite, >= 0 and strictly increasing")
-        pad[p, :B] = t
+        _padded_thresholds(pad, p, r2[p], B)
         v, c = ripley_window(*windows[p], what=f"the window of problem {p}")
         desc[p, 9], desc[p, 10], desc[p, 11] = rows, v.shape[0], 0
         hulls.append(v)
@@ -1029,11 +1028,7 @@ def ripley_launch(xy, checked, K_max, S_max, B_max, seed=0, out=None):
     desc = np.ascontiguousarray(desc, dtype=np.int64)
     r2, hull, cum = (np.ascontiguousarray(a, dtype=np.float64) for a in (r2, hull, cum))
     K_max, S_max, B_max, P = int(K_max), int(S_max), int(B_max), int(desc.shape[0])
-    size = P * K_max * (1 + S_max) * 3 * B_max
-    if out is None:
-        out = torch.empty((P, K_max, 1 + S_max, 3, B_max), dtype=torch.int64, device=xy.device)
-    elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != size:
-        raise ValueError(f"out must be a contiguous int64 tensor of {P} x {K_max} x {1 + S_max} x 3 x {B_max} values")
+    out = _out_int64(out, (P, K_max, 1 + S_max, 3, B_max), xy.device)
     dev = [torch.as_tensor(a, device=xy.device) for a in (desc, r2, hull, cum)]
     launched(model_lib().spadot_ripley_counts(_p(xy), _host(desc), _p(dev[0]), _host(r2), _p(dev[1]), _host(hull), _p(dev[2]),
                                               _host(cum), _p(dev[3]), int(hull.shape[0]), P, K_max, S_max, B_max, _signed64(seed),
