@@ -48,6 +48,7 @@ import time
 import numpy as np
 
 from .utils import _analyze_utils, _utils
+from .utils._stage_utils import cuda_device, open_output, timepoint_masks
 
 ADAPTIVE_KS = list(range(_analyze_utils.MIN_CLUSTERS, _analyze_utils.MAX_CLUSTERS + 1))
 
@@ -106,9 +107,7 @@ def analyze(args):
                          "K-means, and a mixture has no WSS")
     print("Loading latent representations...")
     adata, path = _utils.load_data(args.data)
-    if not getattr(args, "output_dir", None):
-        args.output_dir = os.path.dirname(path) if path else os.getcwd()
-    os.makedirs(args.output_dir, exist_ok=True)
+    open_output(args, path)                               # the prefix of this stage depends on what follows
     if getattr(args, "prefix", None) is None:
         args.prefix = ""
     n_clusters = getattr(args, "n_clusters", None)
@@ -123,8 +122,7 @@ def analyze(args):
     tp_all = np.asarray(adata.obs["timepoint"])
     spatial = np.asarray(adata.obsm["spatial"])
     rows = _rows(adata, X.shape[0])
-    tps = sorted(set(tp_all.tolist()))
-    masks = [tp_all == tp for tp in tps]
+    tps, masks = timepoint_masks(tp_all)
     ks = validate(n_clusters, {tp: int(m.sum()) for tp, m in zip(tps, masks)}, int(X.shape[1]))
     if method == "gmm":
         from .gmm import check_shape
@@ -133,9 +131,7 @@ def analyze(args):
     import torch
     from . import analyze_ot, kmeans
     from .ops import kmeans_assign
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("spadot_amd analyzes on the MI355X only (device 'cuda:N'); there is no CPU path")
+    dev = cuda_device(args, "analyzes")
     timings = {}
     t0 = time.perf_counter()
     print("Clustering...")

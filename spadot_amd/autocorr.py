@@ -35,8 +35,8 @@ import time
 
 import numpy as np
 
-from .moran import centre_spread, columns, degenerate, moran_order, open_stage, refuse_edge_ends, timings
-from .utils._stage_utils import edge_pair, labeling_runs, savez_pinned
+from .moran import centre_spread, columns, degenerate, moran_order, refuse_edge_ends
+from .utils._stage_utils import edge_pair, labeling_runs, open_stage, savez_pinned, timings, top_setting, write_timepoints
 
 FIELDS = ("I", "C", "z_norm_I", "p_norm_I", "z_sim_I", "p_sim_I", "padj_I", "z_norm_C", "p_norm_C", "z_sim_C", "p_sim_C",
           "padj_C", "mean", "pct")
@@ -219,8 +219,7 @@ def autocorr(args):
     import torch
     from .trends import lognorm_values
     t_start = time.perf_counter()
-    top = getattr(args, "top", 100)
-    top = 100 if top is None else int(top)
+    top = top_setting(args, 100)
     k, n_perms, seed = int(getattr(args, "k", 6)), int(getattr(args, "n_perms", 100)), int(getattr(args, "seed", 0))
     if top < 0 or k < 1 or n_perms < 0:
         raise ValueError(f"the autocorr stage takes top >= 0, k >= 1 and n_perms >= 0 (got top = {top}, k = {k}, n_perms = "
@@ -231,18 +230,13 @@ def autocorr(args):
         res = spatial_autocorr(st.edges, dc, lognorm_values(dc), n_perms=n_perms, seed=seed)
     torch.cuda.synchronize(st.dev)
     t_dev = time.perf_counter()
-    tables = {}
     arrays = dict(timepoints=np.asarray(tps), genes=np.asarray(dc.genes).astype(str), k=np.int64(k), n_perms=np.int64(n_perms),
                   seed=np.int64(seed))
-    for tp, r in zip(tps, res):
-        tables[tp] = autocorr_table(r, dc.genes, top)
-        tables[tp].to_csv(st.path(f"autocorr_{tp}.csv"), index=False)
-        for name in ARRAYS:
-            arrays[f"{tp}_{name}"] = getattr(r, name)
-        for name in ("S0", "S1", "S2"):
-            arrays[f"{tp}_{name}"] = np.int64(getattr(r, name))
+    tables, arrays = write_timepoints(st.path, "autocorr", tps, res, lambda t, r: autocorr_table(r, dc.genes, top), ARRAYS, arrays,
+                                      lambda t, r: {name: np.int64(getattr(r, name)) for name in ("S0", "S1", "S2")})
     savez_pinned(st.path("autocorr.npz"), arrays)
     t_end = time.perf_counter()
     print(f"autocorr: {dc.G} genes x {dc.n} spots of {dc.T} time points, k = {k}, {n_perms} permutations, written to "
           f"{args.output_dir}", file=sys.stderr)
-    return {"tables": tables, "results": dict(zip(tps, res)), "timepoints": tps, "timings": timings(st, t_dev, t_end)}
+    return {"tables": tables, "results": dict(zip(tps, res)), "timepoints": tps,
+            "timings": timings(st.t_start, st.t_read, t_dev, t_end, st.t_graph)}

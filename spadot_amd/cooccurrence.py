@@ -44,15 +44,15 @@ as "this pair is not a random labelling", not as "these two interact".
 
 The device counts; the host validates, takes the statistics and writes the files.  Limits: 1 <= K <= 32, 1 <= B <= 64, at most
 2147483391 spots per problem and 65535 problems per call."""
-import os
 import sys
 import time
 
 import numpy as np
 
-from .pairs import MAX_BINS, NO_CPU, counted, default_radii, ladder, mad_p, sorted_problems, thresholds
+from .pairs import MAX_BINS, counted, default_radii, ladder, mad_p, sorted_problems, thresholds
 from .pairs import MAX_CLUSTERS, MAX_PROBLEMS, MAX_SPOTS  # noqa: F401  (handed on with the names above: tests and tools import them from here)
-from .utils._stage_utils import savez_pinned
+from .utils._stage_utils import (cuda_device, open_output, plot_timepoints, read_domains_table, savez_pinned, timings,
+                                 write_timepoints)
 
 TABLE_COLUMNS = ("domain", "neighbor", "radius", "count", "ratio")
 ARRAYS = ("counts", "ratio", "radii", "sizes")
@@ -291,97 +291,59 @@ def cooccur(args):
     S relabelings (args.seed, default 0; time point number g in sorted order draws under problem number g), the files above keep
     their bytes, and the files of _write_null are written beside them with verdicts at args.alpha (default 0.05); the result
     then also holds 'null_tables' and 'summary'."""
-    import pandas as pd
-    from .markers import read_domains
     from .utils import _analyze_utils
     t_start = time.perf_counter()
     null_settings(args)
-    domains = getattr(args, "domains", None)
-    if domains is None or (isinstance(domains, str) and not domains):
-        raise ValueError("the cooccurrence stage needs the domains table of analyze (--domains)")
-    df = pd.read_csv(domains) if isinstance(domains, (str, os.PathLike)) else domains
-    for col in ("pixel_x", "pixel_y", "timepoint", "kmeans"):
-        if col not in df.columns:
-            raise ValueError(f"the domains table has no `{col}` column (expected the domains.csv that analyze writes)")
-    n = len(df)
-    if n == 0:
-        raise ValueError("the domains table is empty")
-    tp_all = np.asarray(df["timepoint"])
-    labels = read_domains(df.assign(row=np.arange(n)), tp_all).astype(np.int64)     # the table's own order; K <= 32 per time point
-    coords = np.stack([np.asarray(df["pixel_x"], dtype=np.float64), np.asarray(df["pixel_y"], dtype=np.float64)], axis=1)
-    if not np.all(np.isfinite(coords)):
-        raise ValueError("the domains table holds spots without finite pixel_x / pixel_y")
+    tab = read_domains_table(args, "cooccurrence")
     bins, ring, radius = int(getattr(args, "bins", 50)), bool(getattr(args, "ring", False)), getattr(args, "radius", None)
     if not 1 <= bins <= MAX_BINS:
         raise ValueError(f"the cooccurrence stage takes 1 to {MAX_BINS} radii (got bins = {bins})")
-    if not getattr(args, "output_dir", None):
-        args.output_dir = (os.path.dirname(os.path.abspath(domains)) if isinstance(domains, (str, os.PathLike))
-                           else os.getcwd())
-    os.makedirs(args.output_dir, exist_ok=True)
-    prefix = getattr(args, "prefix", "") or ""
-    device = getattr(args, "device", None) or "cuda:0"
+    out_file = open_output(args, tab.beside)
 
     import torch
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError(NO_CPU.format("device 'cuda:N'"))
-    tps = sorted(set(tp_all.tolist()))
-    masks = [tp_all == tp for tp in tps]
-    radii = [ladder(radius, bins) if radius is not None else default_radii(coords[m], bins) for m in masks]
-    Ks = [int(labels[m].max()) + 1 for m in masks]
-    n_perms, seed, alpha = null_settings(args, max(Ks), bins)
+    dev = cuda_device(args, "counts co-occurrences")
+    tps, masks = tab.tps, tab.masks
+    radii = [ladder(radius, bins) if radius is not None else default_radii(tab.coords[m], bins) for m in masks]
+    n_perms, seed, alpha = null_settings(args, max(tab.Ks), bins)
     t_read = time.perf_counter()
+    coords, labels = [torch.as_tensor(tab.coords[m], device=dev) for m in masks], [tab.labels[m] for m in masks]
     if n_perms == 0:
-        res = cooccurrence([torch.as_tensor(coords[m], device=dev) for m in masks], [labels[m] for m in masks], radii=radii,
-                           ring=ring, n_clusters=Ks)
+        res = cooccurrence(coords, labels, radii=radii, ring=ring, n_clusters=tab.Ks)
     else:                                                # time point number g in sorted order draws under problem number g
-        res = cooccurrence_null([torch.as_tensor(coords[m], device=dev) for m in masks], [labels[m] for m in masks],
-                                radii=radii, ring=ring, n_perms=n_perms, seed=seed, alpha=alpha, n_clusters=Ks)
+        res = cooccurrence_null(coords, labels, radii=radii, ring=ring, n_perms=n_perms, seed=seed, alpha=alpha, n_clusters=tab.Ks)
     torch.cuda.synchronize(dev)
     t_dev = time.perf_counter()
 
-    tables, arrays = {}, {"timepoints": np.asarray(tps), "bins": np.int64(bins), "ring": np.bool_(ring)}
-    for tp, r in zip(tps, res):
-        tables[tp] = cooccurrence_table(r)
-        tables[tp].to_csv(os.path.join(args.output_dir, f"{prefix}cooccurrence_{tp}.csv"), index=False)
-        for name in ARRAYS:
-            arrays[f"{tp}_{name}"] = getattr(r, name)
-    savez_pinned(os.path.join(args.output_dir, prefix + "cooccurrence.npz"), arrays)
-    if _analyze_utils.have_matplotlib():
-        for tp, r in zip(tps, res):
-            _analyze_utils.plot_cooccurrence(os.path.join(args.output_dir, f"{prefix}{tp}_cooccurrence.png"), r.radii, r.ratio,
-                                             tp, ring)
-    else:
-        print("matplotlib not installed: no plots")
+    head = {"timepoints": np.asarray(tps), "bins": np.int64(bins), "ring": np.bool_(ring)}
+    tables, arrays = write_timepoints(out_file, "cooccurrence", tps, res, lambda t, r: cooccurrence_table(r), ARRAYS, dict(head))
+    savez_pinned(out_file("cooccurrence.npz"), arrays)
+    plot_timepoints(tps, res, lambda tp, r: _analyze_utils.plot_cooccurrence(out_file(f"{tp}_cooccurrence.png"), r.radii,
+                                                                            r.ratio, tp, ring))
     out = {"tables": tables, "results": dict(zip(tps, res)), "timepoints": tps}
     if n_perms:
-        out.update(_write_null(args.output_dir, prefix, tps, res, bins, ring))
+        out.update(_write_null(out_file, tps, res, head, ring))
     t_end = time.perf_counter()
-    print(f"cooccurrence: {n} spots of {len(tps)} time points, {bins} radii{' (rings)' if ring else ''}"
+    print(f"cooccurrence: {tab.n} spots of {len(tps)} time points, {bins} radii{' (rings)' if ring else ''}"
           f"{f', {n_perms} relabelings' if n_perms else ''}, written to {args.output_dir}", file=sys.stderr)
-    out["timings"] = dict(read_s=t_read - t_start, device_s=t_dev - t_read, write_s=t_end - t_dev, total_s=t_end - t_start)
+    out["timings"] = timings(t_start, t_read, t_dev, t_end)
     return out
 
 
-def _write_null(output_dir, prefix, tps, res, bins, ring):
+def _write_null(out_file, tps, res, head, ring):
     """The files of the null beside the stage's own: {prefix}cooccurrence_null_{tp}.csv (NULL_TABLE_COLUMNS),
     {prefix}cooccurrence_summary.csv (NULL_SUMMARY_COLUMNS), {prefix}cooccurrence_null.npz ('{tp}_' + each of NULL_ARRAYS, plus
-    timepoints, bins, ring, n_perms, seed, alpha) and, with matplotlib, {prefix}{tp}_cooccurrence_null.png.  Returns
-    {'null_tables', 'summary'}."""
+    timepoints, bins, ring -- `head` -- and n_perms, seed, alpha) and, with matplotlib, {prefix}{tp}_cooccurrence_null.png.
+    Returns {'null_tables', 'summary'}."""
     from .utils import _analyze_utils
     r0 = res[0]
-    tables, arrays = {}, {"timepoints": np.asarray(tps), "bins": np.int64(bins), "ring": np.bool_(ring),
-                          "n_perms": np.int64(r0.n_perms), "seed": np.int64(r0.seed), "alpha": np.float64(r0.alpha)}
-    for tp, r in zip(tps, res):
-        tables[tp] = cooccurrence_null_table(r)
-        tables[tp].to_csv(os.path.join(output_dir, f"{prefix}cooccurrence_null_{tp}.csv"), index=False)
-        for name in NULL_ARRAYS:
-            arrays[f"{tp}_{name}"] = np.asarray(getattr(r, name))
+    head = dict(head, n_perms=np.int64(r0.n_perms), seed=np.int64(r0.seed), alpha=np.float64(r0.alpha))
+    tables, arrays = write_timepoints(out_file, "cooccurrence_null", tps, res, lambda t, r: cooccurrence_null_table(r), NULL_ARRAYS,
+                                      head)
     summary = cooccurrence_null_summary(tps, res)
-    summary.to_csv(os.path.join(output_dir, prefix + "cooccurrence_summary.csv"), index=False)
-    savez_pinned(os.path.join(output_dir, prefix + "cooccurrence_null.npz"), arrays)
+    summary.to_csv(out_file("cooccurrence_summary.csv"), index=False)
+    savez_pinned(out_file("cooccurrence_null.npz"), arrays)
     if _analyze_utils.have_matplotlib():
         for tp, r in zip(tps, res):
-            _analyze_utils.plot_cooccurrence_null(os.path.join(output_dir, f"{prefix}{tp}_cooccurrence_null.png"), r.radii, r.ratio,
-                                                  r.ratio_sim_min, r.ratio_sim_max, tp, ring, r.relation)
+            _analyze_utils.plot_cooccurrence_null(out_file(f"{tp}_cooccurrence_null.png"), r.radii, r.ratio, r.ratio_sim_min,
+                                                  r.ratio_sim_max, tp, ring, r.relation)
     return {"null_tables": tables, "summary": summary}

@@ -21,6 +21,7 @@
 #include <cstdint>
 
 #include "../../include/spadot_model.h"
+#include "csc_walk.h"
 
 typedef unsigned long long mk_u64;
 
@@ -32,14 +33,6 @@ typedef unsigned long long mk_u64;
 #define MK_MAX_LONG 1024           // workgroups (and slabs) of the long path: 4 per CU
 #define MK_SLAB_BYTES (1ll << 30)  // most scratch the slabs of the long path take together
 #define MK_HEAD 256                // bytes ahead of the queue: the counter
-
-__device__ __forceinline__ long long mk_lower_bound(const int *idx, long long lo, long long hi, int key) {
-    while (lo < hi) {
-        const long long mid = lo + ((hi - lo) >> 1);
-        if (idx[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 static inline long long mk_pow2(long long n) {
     long long p = 4;
@@ -201,8 +194,8 @@ __global__ void __launch_bounds__(MK_THREADS) k_mk_ranksum(const long long *colp
     __shared__ mk_u64 s_ties;
     const int item = blockIdx.x;
     const int t = item / G, g = item % G;
-    const long long lo = mk_lower_bound(ridx, colptr[g], colptr[g + 1], tp_off[t]);
-    const long long hi = mk_lower_bound(ridx, lo, colptr[g + 1], tp_off[t + 1]);
+    const long long lo = csc_walk_lower_bound(ridx, colptr[g], colptr[g + 1], tp_off[t]);
+    const long long hi = csc_walk_lower_bound(ridx, lo, colptr[g + 1], tp_off[t + 1]);
     const long long len = hi - lo;
     if (len > MK_CAP) {                                  // uniform over the workgroup
         if (threadIdx.x == 0) queue[atomicAdd(queue_n, 1)] = item;
@@ -238,8 +231,8 @@ __global__ void __launch_bounds__(MK_THREADS) k_mk_ranksum_long(const long long 
     for (int q = blockIdx.x; q < count; q += gridDim.x) {
         const int item = queue[q];
         const int t = item / G, g = item % G;
-        const long long lo = mk_lower_bound(ridx, colptr[g], colptr[g + 1], tp_off[t]);
-        const long long hi = mk_lower_bound(ridx, lo, colptr[g + 1], tp_off[t + 1]);
+        const long long lo = csc_walk_lower_bound(ridx, colptr[g], colptr[g + 1], tp_off[t]);
+        const long long hi = csc_walk_lower_bound(ridx, lo, colptr[g + 1], tp_off[t + 1]);
         const long long m = hi - lo;
         long long P = 2 * MK_CAP;
         while (P < m) P <<= 1;

@@ -16,6 +16,7 @@
 #include <cstdint>
 
 #include "../../include/spadot_model.h"
+#include "csc_walk.h"
 
 #define PRE_WAVE 64
 #define PRE_WAVES 4                // wavefronts per 256-thread workgroup, one item each
@@ -36,15 +37,6 @@ __device__ __forceinline__ int pre_wave_sum_i(int x) {
     return x;
 }
 
-// first position p in [lo, hi) with idx[p] >= key (hi if none)
-__device__ __forceinline__ long long pre_lower_bound(const int *idx, long long lo, long long hi, int key) {
-    while (lo < hi) {
-        const long long mid = lo + ((hi - lo) >> 1);
-        if (idx[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // time point of a row: tp_off is short (one entry per time point), a linear scan is enough
 __device__ __forceinline__ int pre_row_tp(const int *tp_off, int T, int row) {
     int t = 0;
@@ -59,8 +51,8 @@ __global__ void __launch_bounds__(256) k_pre_gene_detect(const long long *colptr
     const long long item = (long long)blockIdx.x * PRE_WAVES + (threadIdx.x >> 6);
     if (item >= (long long)T * G) return;
     const int t = (int)(item / G), g = (int)(item % G);
-    const long long a = pre_lower_bound(ridx, colptr[g], colptr[g + 1], tp_off[t]);
-    const long long b = pre_lower_bound(ridx, a, colptr[g + 1], tp_off[t + 1]);
+    const long long a = csc_walk_lower_bound(ridx, colptr[g], colptr[g + 1], tp_off[t]);
+    const long long b = csc_walk_lower_bound(ridx, a, colptr[g + 1], tp_off[t + 1]);
     int c = 0;
     double s = 0.0;
     for (long long p = a + lane; p < b; p += PRE_WAVE) {
@@ -100,8 +92,8 @@ __global__ void __launch_bounds__(256) k_sparkx_moments(const long long *colptr,
     const int item = blockIdx.x * PRE_WAVES + (threadIdx.x >> 6);
     if (item >= P) return;
     const int t = pair_t[item], g = pair_g[item];
-    const long long a = pre_lower_bound(ridx, colptr[g], colptr[g + 1], tp_off[t]);
-    const long long b = pre_lower_bound(ridx, a, colptr[g + 1], tp_off[t + 1]);
+    const long long a = csc_walk_lower_bound(ridx, colptr[g], colptr[g + 1], tp_off[t]);
+    const long long b = csc_walk_lower_bound(ridx, a, colptr[g + 1], tp_off[t + 1]);
     double acc[PRE_NM];
 #pragma unroll
     for (int k = 0; k < PRE_NM; ++k) acc[k] = 0.0;
@@ -211,8 +203,8 @@ __global__ void __launch_bounds__(256) k_pre_lognorm_stats(const long long *colp
     const long long item = (long long)blockIdx.x * PRE_WAVES + (threadIdx.x >> 6);
     if (item >= (long long)T * S) return;
     const int t = (int)(item / S), g = cols[item % S];
-    const long long a = pre_lower_bound(ridx, colptr[g], colptr[g + 1], tp_off[t]);
-    const long long b = pre_lower_bound(ridx, a, colptr[g + 1], tp_off[t + 1]);
+    const long long a = csc_walk_lower_bound(ridx, colptr[g], colptr[g + 1], tp_off[t]);
+    const long long b = csc_walk_lower_bound(ridx, a, colptr[g + 1], tp_off[t + 1]);
     const double n = (double)(tp_off[t + 1] - tp_off[t]);
     double s = 0.0;
     for (long long p = a + lane; p < b; p += PRE_WAVE) s += pre_lognorm(val[p], total[ridx[p]], target);

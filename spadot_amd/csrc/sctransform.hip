@@ -21,6 +21,7 @@
 #include <cstdint>
 
 #include "../../include/spadot_model.h"
+#include "csc_walk.h"
 
 #define SCT_WAVE 64
 #define SCT_WAVES 4                 // wavefronts per 256-thread workgroup, one gene each
@@ -31,15 +32,6 @@ __device__ __forceinline__ double sct_wave_sum(double x) {
 #pragma unroll
     for (int off = SCT_WAVE / 2; off > 0; off >>= 1) x += __shfl_xor(x, off, SCT_WAVE);
     return x;
-}
-
-// first position p in [lo, hi) with idx[p] >= key (hi if none)
-__device__ __forceinline__ long long sct_lower_bound(const int *idx, long long lo, long long hi, int key) {
-    while (lo < hi) {
-        const long long mid = lo + ((hi - lo) >> 1);
-        if (idx[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 __device__ __forceinline__ double sct_clamp(double v, double c) { return v < -c ? -c : (v > c ? c : v); }
@@ -81,8 +73,8 @@ __global__ void __launch_bounds__(256) k_sct_gene_stats(const long long *colptr,
     const int item = blockIdx.x * SCT_WAVES + (threadIdx.x >> 6);
     if (item >= Gk) return;
     const int g = genes[item];
-    const long long a = sct_lower_bound(ridx, colptr[g], colptr[g + 1], tp_off[t]);
-    const long long b = sct_lower_bound(ridx, a, colptr[g + 1], tp_off[t + 1]);
+    const long long a = csc_walk_lower_bound(ridx, colptr[g], colptr[g + 1], tp_off[t]);
+    const long long b = csc_walk_lower_bound(ridx, a, colptr[g + 1], tp_off[t + 1]);
     double sl = 0.0, sy = 0.0;
     for (long long p = a + lane; p < b; p += SCT_WAVE) {
         const double y = (double)val[p];
@@ -119,8 +111,8 @@ __global__ void __launch_bounds__(256) k_sct_fit(const long long *colptr, const 
     const int item = blockIdx.x * SCT_WAVES + (threadIdx.x >> 6);
     if (item >= G1) return;
     const int g = genes[item];
-    const long long a = sct_lower_bound(ridx, colptr[g], colptr[g + 1], tp_off[t]);
-    const long long b = sct_lower_bound(ridx, a, colptr[g + 1], tp_off[t + 1]);
+    const long long a = csc_walk_lower_bound(ridx, colptr[g], colptr[g + 1], tp_off[t]);
+    const long long b = csc_walk_lower_bound(ridx, a, colptr[g + 1], tp_off[t + 1]);
     const double n = (double)N;
     double sy = 0.0, sxy = 0.0;                       // X^T y: constant over the iterations, sparse
     for (long long p = a + lane; p < b; p += SCT_WAVE) {
@@ -206,8 +198,8 @@ __global__ void __launch_bounds__(256) k_sct_resid_stats(const long long *colptr
     const int item = blockIdx.x * SCT_WAVES + (threadIdx.x >> 6);
     if (item >= Gk) return;
     const int g = genes[item];
-    const long long a = sct_lower_bound(ridx, colptr[g], colptr[g + 1], tp_off[t]);
-    const long long b = sct_lower_bound(ridx, a, colptr[g + 1], tp_off[t + 1]);
+    const long long a = csc_walk_lower_bound(ridx, colptr[g], colptr[g + 1], tp_off[t]);
+    const long long b = csc_walk_lower_bound(ridx, a, colptr[g + 1], tp_off[t + 1]);
     const double th = pars[(long long)item * 3 + 0], b0 = pars[(long long)item * 3 + 1], b1 = pars[(long long)item * 3 + 2];
     const double n = (double)N;
     double s = 0.0, s30 = 0.0;
@@ -268,10 +260,10 @@ __global__ void __launch_bounds__(256) k_sct_resid_write(const long long *colptr
     }
     __syncthreads();
     const int g = genes[i];
-    const long long a = sct_lower_bound(ridx, colptr[g], colptr[g + 1], tp_off[t]);
-    const long long b = sct_lower_bound(ridx, a, colptr[g + 1], tp_off[t + 1]);
-    const long long pa = sct_lower_bound(ridx, a, b, krow[k0]);
-    const long long pb = k0 + nk < N ? sct_lower_bound(ridx, pa, b, krow[k0 + nk]) : b;
+    const long long a = csc_walk_lower_bound(ridx, colptr[g], colptr[g + 1], tp_off[t]);
+    const long long b = csc_walk_lower_bound(ridx, a, colptr[g + 1], tp_off[t + 1]);
+    const long long pa = csc_walk_lower_bound(ridx, a, b, krow[k0]);
+    const long long pb = k0 + nk < N ? csc_walk_lower_bound(ridx, pa, b, krow[k0 + nk]) : b;
     for (long long p = pa + threadIdx.x; p < pb; p += blockDim.x) {
         const int r = ridx[p];
         const int k = rowmap[r] - k0;

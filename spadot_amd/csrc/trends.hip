@@ -25,6 +25,7 @@
 #include <cstdint>
 
 #include "../../include/spadot_model.h"
+#include "csc_walk.h"
 
 #define TR_THREADS 256
 #define TR_WAVE 64
@@ -34,14 +35,6 @@
 #ifndef TR_VW
 #define TR_VW 1                    // columns per load and lane: 1 (8-byte loads) or 2 (16-byte loads)
 #endif
-
-__device__ __forceinline__ long long tr_lower_bound(const int *idx, long long lo, long long hi, int key) {
-    while (lo < hi) {
-        const long long mid = lo + ((hi - lo) >> 1);
-        if (idx[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 // one stored entry (row i, value x) into the lane's accumulators; w: the lane's NJ columns of row i
 template <int NJ>
@@ -76,8 +69,8 @@ __global__ void __launch_bounds__(TR_THREADS) k_tr_moments(const long long *__re
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const long long item = blockIdx.x;
     const int t = (int)(item / G), g = (int)(item % G);
-    const long long lo = tr_lower_bound(ridx, colptr[g], colptr[g + 1], tp_off[t]);
-    const long long hi = tr_lower_bound(ridx, lo, colptr[g + 1], tp_off[t + 1]);
+    const long long lo = csc_walk_lower_bound(ridx, colptr[g], colptr[g + 1], tp_off[t]);
+    const long long hi = csc_walk_lower_bound(ridx, lo, colptr[g + 1], tp_off[t + 1]);
     const int m = (int)(hi - lo);                        // <= the spots of the time point < 2^31
 
     // slot s of the lane: the columns VW * (lane + 64 s) .. + VW - 1, as accumulators s * VW .. ; a load past the row's end is

@@ -35,9 +35,9 @@ import time
 
 import numpy as np
 
-from .moran import centre_spread, columns, degenerate, edge_csr, gene_selection, open_stage, timings, top_genes
+from .moran import centre_spread, columns, degenerate, edge_csr, gene_selection, top_genes
 from .moran import read_genes  # noqa: F401  (the --genes of this stage: callers import it from here)
-from .utils._stage_utils import edge_pair, savez_pinned
+from .utils._stage_utils import edge_pair, open_stage, read_domains, savez_pinned, timings, top_setting, write_timepoints
 
 FIELDS = ("I", "quadrant", "p_sim", "padj", "lag", "ge", "le")
 TABLE_COLUMNS = ("gene", "I", "n_HH", "n_LL", "n_LH", "n_HL")
@@ -225,11 +225,9 @@ def hotspots(args):
     'domain_tables', 'results' (per time point), 'genes', 'timepoints', 'timings'}."""
     import torch
     from .autocorr import spatial_autocorr
-    from .markers import read_domains
     from .trends import lognorm_values
     t_start = time.perf_counter()
-    top = getattr(args, "top", 50)
-    top = 50 if top is None else int(top)
+    top = top_setting(args, 50)
     k, n_perms, seed = int(getattr(args, "k", 6)), int(getattr(args, "n_perms", 999)), int(getattr(args, "seed", 0))
     alpha = getattr(args, "alpha", 0.05)
     alpha, fdr = 0.05 if alpha is None else float(alpha), bool(getattr(args, "fdr", False))
@@ -249,21 +247,17 @@ def hotspots(args):
         res = local_moran(st.edges, dc, sel, values, n_perms=n_perms, seed=seed)
     torch.cuda.synchronize(st.dev)
     t_dev = time.perf_counter()
-    tables, domain_tables = {}, {}
     arrays = dict(timepoints=np.asarray(tps), genes=np.asarray(dc.genes).astype(str)[sel], k=np.int64(k), n_perms=np.int64(n_perms),
                   seed=np.int64(seed), alpha=np.float64(alpha))
-    for t, (tp, r) in enumerate(zip(tps, res)):
-        tables[tp] = hotspot_table(r, dc.genes, alpha, fdr)
-        tables[tp].to_csv(st.path(f"hotspots_{tp}.csv"), index=False)
-        for name in FIELDS:
-            arrays[f"{tp}_{name}"] = getattr(r, name)
-        arrays[f"{tp}_spots"] = np.asarray(dc.perm[st.rows(t)], dtype=np.int64)
-        if labels is not None:
-            domain_tables[tp] = domain_table(r, dc.genes, labels[dc.perm[st.rows(t)]], alpha, fdr)
-            domain_tables[tp].to_csv(st.path(f"hotspots_domains_{tp}.csv"), index=False)
+    tables, arrays = write_timepoints(st.path, "hotspots", tps, res, lambda t, r: hotspot_table(r, dc.genes, alpha, fdr), FIELDS,
+                                      arrays, lambda t, r: {"spots": np.asarray(dc.perm[st.rows(t)], dtype=np.int64)})
+    domain_tables = {}
+    if labels is not None:
+        domain_tables, _ = write_timepoints(st.path, "hotspots_domains", tps, res, lambda t, r: domain_table(
+            r, dc.genes, labels[dc.perm[st.rows(t)]], alpha, fdr), ())
     savez_pinned(st.path("hotspots.npz"), arrays)
     t_end = time.perf_counter()
     print(f"hotspots: {sel.size} genes x {dc.n} spots of {dc.T} time points, k = {k}, {n_perms} permutations, written to "
           f"{args.output_dir}", file=sys.stderr)
     return {"tables": tables, "domain_tables": domain_tables, "results": dict(zip(tps, res)), "genes": sel, "timepoints": tps,
-            "timings": timings(st, t_dev, t_end)}
+            "timings": timings(st.t_start, st.t_read, t_dev, t_end, st.t_graph)}

@@ -35,7 +35,8 @@ import time
 
 import numpy as np
 
-from .utils._stage_utils import labeling_runs, savez_pinned
+from .utils._stage_utils import (cuda_device, labeling_runs, load_marker_counts, open_output, read_domains, savez_pinned, timings,
+                                 top_setting, write_timepoints)
 
 FIELDS = ("mean", "pvalue", "padj", "gene_mean", "gene_pct", "sizes", "tested", "ge")
 TABLE_COLUMNS = ("source", "target", "domain_source", "domain_target", "mean", "pvalue", "padj", "mean_source", "mean_target",
@@ -317,20 +318,15 @@ def interactions(args):
     stamps: two runs with one seed write the same bytes).  Returns {'tables', 'results' (per time point), 'timepoints',
     'timings'}."""
     import torch
-    from .markers import load_marker_counts, read_domains
     from .preprocess import DeviceCounts
     t_start = time.perf_counter()
-    top = getattr(args, "top", 100)
-    top = 100 if top is None else int(top)
+    top = top_setting(args, 100)
     n_perms, seed = int(getattr(args, "n_perms", 1000)), int(getattr(args, "seed", 0))
     threshold = float(getattr(args, "threshold", 0.1))
     if top < 0 or n_perms < 0 or not 0.0 <= threshold <= 1.0:
         raise ValueError(f"the ligrec stage takes top >= 0, n_perms >= 0 and 0 <= threshold <= 1 (got top = {top}, n_perms = "
                          f"{n_perms}, threshold = {threshold})")
-    device = getattr(args, "device", None) or "cuda:0"
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("spadot_amd takes the ligand-receptor test on the MI355X only (device 'cuda:N'); there is no CPU path")
+    dev = cuda_device(args, "takes the ligand-receptor test")
     if not getattr(args, "domains", None):
         raise ValueError("the ligrec stage needs the domains table of analyze (--domains)")
     if not getattr(args, "interactions", None):
@@ -338,27 +334,18 @@ def interactions(args):
     raw, path = load_marker_counts(args.data)
     labels = read_domains(args.domains, raw.obs["timepoint"])
     pairs = read_interactions(args.interactions, raw.var_names)
-    if not getattr(args, "output_dir", None):
-        args.output_dir = os.path.dirname(path) if path else os.getcwd()
-    os.makedirs(args.output_dir, exist_ok=True)
-    prefix = getattr(args, "prefix", "") or ""
+    out_file = open_output(args, path)
     dc = DeviceCounts(raw, dev)
     tps = [str(t) for t in dc.tps]
     t_read = time.perf_counter()
     res = ligrec(dc, labels, pairs, n_perms=n_perms, seed=seed, threshold=threshold)
     torch.cuda.synchronize(dev)
     t_dev = time.perf_counter()
-    tables = {}
     arrays = dict(sources=res[0].sources, targets=res[0].targets, genes=res[0].genes, timepoints=np.asarray(tps),
                   n_perms=np.int64(n_perms), seed=np.int64(seed), threshold=np.float64(threshold))
-    for tp, r in zip(tps, res):
-        tables[tp] = ligrec_table(r, top)
-        tables[tp].to_csv(os.path.join(args.output_dir, f"{prefix}ligrec_{tp}.csv"), index=False)
-        for name in FIELDS:
-            arrays[f"{tp}_{name}"] = getattr(r, name)
-    savez_pinned(os.path.join(args.output_dir, prefix + "ligrec.npz"), arrays)
+    tables, arrays = write_timepoints(out_file, "ligrec", tps, res, lambda t, r: ligrec_table(r, top), FIELDS, arrays)
+    savez_pinned(out_file("ligrec.npz"), arrays)
     t_end = time.perf_counter()
     print(f"ligrec: {pairs.shape[0]} interactions over {res[0].genes.shape[0]} genes x {dc.n} spots of {dc.T} time points, "
           f"{n_perms} permutations, written to {args.output_dir}", file=sys.stderr)
-    return {"tables": tables, "results": dict(zip(tps, res)), "timepoints": tps,
-            "timings": dict(read_s=t_read - t_start, device_s=t_dev - t_read, write_s=t_end - t_dev, total_s=t_end - t_start)}
+    return {"tables": tables, "results": dict(zip(tps, res)), "timepoints": tps, "timings": timings(t_start, t_read, t_dev, t_end)}

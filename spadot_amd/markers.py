@@ -17,14 +17,15 @@ time point (the others: score 0, pval = padj = 1).
 
 The device ranks; the host does the plumbing (row permutation, CSR -> CSC, domain sizes, means from the device's sums, BH,
 ordering and the files)."""
-import os
 import sys
 import time
 
 import numpy as np
 
 from ._call import launched, ptr as _p, stream as _stream
-from .utils._preprocess_utils import RawCounts, _to_csr, load_counts, timepoint_order
+from .utils._preprocess_utils import RawCounts, load_counts, timepoint_order
+from .utils._stage_utils import load_marker_counts, read_domains  # noqa: F401  (handed on: they were first written for this stage)
+from .utils._stage_utils import open_output, top_setting
 
 TARGET_SUM = 1e4
 MAX_DOMAINS = 32               # the cap of analyze; the kernel's accumulators are sized for it
@@ -207,62 +208,6 @@ def find_markers(counts, labels, device="cuda:0"):
     return out
 
 
-def load_marker_counts(data):
-    """The counts the markers stage reads: the .npz `preprocess` writes (its X holds scaled values; the raw counts of the
-    selected genes are its counts_data / counts_indices / counts_indptr / counts_shape), or anything load_counts reads.
-    Returns (RawCounts, absolute path or None)."""
-    if isinstance(data, (str, os.PathLike)) and str(data).endswith(".npz"):
-        path = os.path.abspath(data)
-        z = np.load(path, allow_pickle=False)
-        if "counts_data" in z.files:
-            import scipy.sparse as sp
-            for key in ("timepoint", "spatial"):
-                if key not in z.files:
-                    raise ValueError(f"{path} has no `{key}` array")
-            shape = tuple(int(v) for v in z["counts_shape"])
-            X = sp.csr_matrix((z["counts_data"], z["counts_indices"], z["counts_indptr"]), shape=shape)
-            genes = z["genes"] if "genes" in z.files else np.arange(shape[1]).astype(str)
-            if len(z["timepoint"]) != shape[0] or len(genes) != shape[1]:
-                raise ValueError(f"{path}: counts of shape {shape} against {len(z['timepoint'])} time point entries and "
-                                 f"{len(genes)} gene names")
-            return RawCounts(_to_csr(X), z["timepoint"], np.asarray(z["spatial"], dtype=np.float64), genes), path
-    return load_counts(data)
-
-
-def read_domains(domains, timepoint):
-    """Domain label of every row of the data from the domains table of analyze (columns row, timepoint, kmeans; a path or a
-    DataFrame).  `timepoint`: the data's time point per row.  Every row must be labelled exactly once, with the data's time
-    point, and no time point may have more than 32 domains: ValueError otherwise."""
-    import pandas as pd
-    df = pd.read_csv(domains) if isinstance(domains, (str, os.PathLike)) else domains
-    for col in ("row", "timepoint", "kmeans"):
-        if col not in df.columns:
-            raise ValueError(f"the domains table has no `{col}` column (expected the domains.csv that analyze writes)")
-    tp = np.asarray(timepoint)
-    n = tp.shape[0]
-    row = np.asarray(df["row"])
-    if row.dtype.kind not in "iu":
-        raise ValueError("the `row` column of the domains table must hold integer row numbers of the data")
-    if row.size and (row.min() < 0 or row.max() >= n):
-        raise ValueError(f"the domains table names row {int(row.max() if row.max() >= n else row.min())}: the data has rows "
-                         f"0 .. {n - 1}")
-    seen = np.bincount(row, minlength=n)
-    if np.any(seen > 1):
-        raise ValueError(f"row {int(np.flatnonzero(seen > 1)[0])} is labelled more than once in the domains table "
-                         f"({int((seen > 1).sum())} duplicate rows)")
-    if np.any(seen == 0):
-        raise ValueError(f"row {int(np.flatnonzero(seen == 0)[0])} of the data has no label in the domains table "
-                         f"({int((seen == 0).sum())} missing rows)")
-    bad = np.flatnonzero(np.asarray(df["timepoint"]).astype(str) != tp[row].astype(str))
-    if bad.size:
-        r = int(row[bad[0]])
-        raise ValueError(f"time point mismatch at row {r}: the domains table says {df['timepoint'].iloc[int(bad[0])]!r}, the "
-                         f"data says {tp[r]!r} ({bad.size} rows differ)")
-    labels = np.empty(n, dtype=np.int64)
-    labels[row] = np.asarray(df["kmeans"])
-    return check_labels(labels, tp)[0]
-
-
 def marker_table(res, t, top=100):
     """The rows of {prefix}markers_{tp}.csv: per domain the `top` highest scores (0 = all), ordered by domain, then score
     descending, then gene column."""
@@ -288,24 +233,17 @@ def markers(args):
     if not getattr(args, "domains", None):
         raise ValueError("the markers stage needs the domains table of analyze (--domains)")
     labels = read_domains(args.domains, raw.obs["timepoint"])
-    if not getattr(args, "output_dir", None):
-        args.output_dir = os.path.dirname(path) if path else os.getcwd()
-    os.makedirs(args.output_dir, exist_ok=True)
-    prefix = getattr(args, "prefix", "") or ""
-    top = getattr(args, "top", 100)
-    top = 100 if top is None else int(top)
-    if top < 0:
-        raise ValueError(f"top must be 0 (all genes) or a positive count, not {top}")
-    device = getattr(args, "device", None) or "cuda:0"
-    res = find_markers(raw, labels, device=device)
+    out_file = open_output(args, path)
+    top = top_setting(args, 100, least=0)
+    res = find_markers(raw, labels, device=getattr(args, "device", None) or "cuda:0")
     arrays = dict(genes=np.asarray(res["genes"]).astype(str), timepoints=np.asarray([str(t) for t in res["timepoints"]]))
     names = []
     for t, tp in enumerate(res["timepoints"]):
-        marker_table(res, t, top).to_csv(os.path.join(args.output_dir, f"{prefix}markers_{tp}.csv"), index=False)
+        marker_table(res, t, top).to_csv(out_file(f"markers_{tp}.csv"), index=False)
         for c in COLUMNS + ("U1",):
             arrays[f"{c}_{t}"] = res[c][t]
         names += [f"{tp}_{k}" for k in range(res["score"][t].shape[1])]
     arrays["domains"] = np.asarray(names)
-    np.savez(os.path.join(args.output_dir, prefix + "markers.npz"), **arrays)
+    np.savez(out_file("markers.npz"), **arrays)
     print(f"markers: {len(names)} domains x {len(res['genes'])} genes written to {args.output_dir}", file=sys.stderr)
     return res

@@ -40,8 +40,8 @@ import time
 
 import numpy as np
 
-from .moran import centre_spread, columns, degenerate, edge_csr, gene_selection, open_stage, read_genes, timings, top_genes
-from .utils._stage_utils import edge_pair, labeling_runs, savez_pinned
+from .moran import centre_spread, columns, degenerate, edge_csr, gene_selection, read_genes, top_genes
+from .utils._stage_utils import edge_pair, labeling_runs, open_stage, savez_pinned, timings, top_setting, write_timepoints
 
 FIELDS = ("R", "z_sim", "p_sim", "padj")
 TABLE_COLUMNS = ("gene", "module", "I", "R_own", "best_other", "R_other")
@@ -345,7 +345,7 @@ def modules(args):
         v = getattr(args, name, default)
         return kind(default if v is None else v)
 
-    top, k, n_perms, seed = arg("top", 100, int), arg("k", 6, int), arg("n_perms", 100, int), arg("seed", 0, int)
+    top, k, n_perms, seed = top_setting(args, 100), arg("k", 6, int), arg("n_perms", 100, int), arg("seed", 0, int)
     min_sim, min_genes, alpha = arg("min_sim", MIN_SIM, float), arg("min_genes", MIN_GENES, int), arg("alpha", 0.05, float)
     top_pairs = arg("top_pairs", 0, int)
     if top < 1 or k < 1 or n_perms < 1 or not min_sim <= 1.0 or min_genes < 1 or not 0.0 < alpha <= 1.0 or top_pairs < 0:
@@ -366,21 +366,14 @@ def modules(args):
         scores = [module_scores(r.z, r.m2, r.n, lab) for r, lab in zip(res, labels)]
     torch.cuda.synchronize(st.dev)
     t_dev = time.perf_counter()
-    tables, pair_tables = {}, {}
     arrays = dict(timepoints=np.asarray(tps), genes=np.asarray(dc.genes).astype(str)[sel], k=np.int64(k), n_perms=np.int64(n_perms),
                   seed=np.int64(seed), min_sim=np.float64(min_sim), min_genes=np.int64(min_genes), alpha=np.float64(alpha))
-    significant = 0
-    for t, (tp, r) in enumerate(zip(tps, res)):
-        tables[tp] = module_table(r, dc.genes, labels[t])
-        tables[tp].to_csv(st.path(f"modules_{tp}.csv"), index=False)
-        pair_tables[tp] = pair_table(r, dc.genes, labels[t], top_pairs)
-        pair_tables[tp].to_csv(st.path(f"modules_pairs_{tp}.csv"), index=False)
-        for name in FIELDS:
-            arrays[f"{tp}_{name}"] = getattr(r, name)
-        arrays[f"{tp}_module"], arrays[f"{tp}_scores"] = labels[t], scores[t]
-        arrays[f"{tp}_spots"] = np.asarray(dc.perm[st.rows(t)], dtype=np.int64)
-        with np.errstate(invalid="ignore"):
-            significant += int((r.padj[np.triu_indices(sel.size, 1)] <= alpha).sum())
+    tables, arrays = write_timepoints(st.path, "modules", tps, res, lambda t, r: module_table(r, dc.genes, labels[t]), FIELDS, arrays,
+                                      lambda t, r: {"module": labels[t], "scores": scores[t],
+                                                    "spots": np.asarray(dc.perm[st.rows(t)], dtype=np.int64)})
+    pair_tables, _ = write_timepoints(st.path, "modules_pairs", tps, res, lambda t, r: pair_table(r, dc.genes, labels[t], top_pairs), ())
+    with np.errstate(invalid="ignore"):
+        significant = sum(int((r.padj[np.triu_indices(sel.size, 1)] <= alpha).sum()) for r in res)
     overlap = overlap_table(tps, labels)
     overlap.to_csv(st.path("modules_overlap.csv"), index=False)
     savez_pinned(st.path("modules.npz"), arrays)
@@ -390,4 +383,4 @@ def modules(args):
           f"{args.output_dir}", file=sys.stderr)
     return {"tables": tables, "pair_tables": pair_tables, "overlap": overlap, "results": dict(zip(tps, res)),
             "modules": dict(zip(tps, labels)), "scores": dict(zip(tps, scores)), "genes": sel, "timepoints": tps,
-            "timings": timings(st, t_dev, t_end)}
+            "timings": timings(st.t_start, st.t_read, t_dev, t_end, st.t_graph)}

@@ -1,6 +1,7 @@
 """What the three Moran stages share on the host: autocorr (Moran's I and Geary's C per gene), hotspots (local Moran's I) and modules
 (bivariate Moran's I) work on the same graph, the same values with the same centre and spread, one degeneracy rule, one selection
-of genes and one stage frame.  Every rule is written here once.
+of genes.  Every rule is written here once.  The frame of their drivers is the one every stage has
+(utils/_stage_utils.py: Stage, open_stage and timings are handed on from here).
 
     columns(data, values)                the data of a call as one object: a DeviceCounts with its values, or dense columns as a CSC
     column_moments(cols)                 per (time point, gene) the stored count, sum v and sum v^2
@@ -10,12 +11,12 @@ of genes and one stage frame.  Every rule is written here once.
     refuse_edge_ends(pairs, sizes)       edge ends outside 0 .. n-1, before they are narrowed to int32 or sorted
     edge_csr(pairs, sizes, device)       the CSR of every time point: the edges sorted stably by source
     read_genes(spec, names)              the gene indices of --genes
-    moran_order(I), top_genes(res, top)  the genes by descending Moran's I, and the union of the first `top` over the time points
-    open_stage(..), timings(..)          what the three stages do before and after their own part"""
+    moran_order(I), top_genes(res, top)  the genes by descending Moran's I, and the union of the first `top` over the time points"""
 import os
-import time
 
 import numpy as np
+
+from .utils._stage_utils import Stage, open_stage, timings  # noqa: F401  (handed on: the stages and their tests took them from here)
 
 
 class Columns:
@@ -173,52 +174,3 @@ def top_genes(results, top):
     for r in results:
         picked.update(int(g) for g in moran_order(r.I)[:top] if not np.isnan(r.I[g]))
     return np.asarray(sorted(picked), dtype=np.int32)
-
-
-class Stage:
-    """What open_stage hands to a stage: dev, dc (the DeviceCounts), tps, off (dc.tp_off_host), edges (spatial_edges per time
-    point), prefix, out_dir, extras (what the stage's own `resolve` returned) and the clock marks t_start, t_read, t_graph."""
-
-    def path(self, name):
-        return os.path.join(self.out_dir, self.prefix + name)
-
-    def rows(self, t):
-        """The rows of time point t in the order of the DeviceCounts."""
-        return slice(int(self.off[t]), int(self.off[t + 1]))
-
-
-def open_stage(args, k, what, t_start, resolve=None):
-    """The opening of a Moran stage: the device must be cuda ("spadot_amd takes {what} on the MI355X only"), the counts of
-    args.data are read (markers.load_marker_counts), resolve(raw) takes what the stage reads of its other arguments -- before
-    anything is written, so that an unknown name raises first --, args.output_dir defaults to the directory of the data and is
-    created, the counts go to the device, the coordinates must be finite and every time point gets its spatial_edges(.., k)."""
-    import torch
-    from .markers import load_marker_counts
-    from .neighbors import spatial_edges
-    from .preprocess import DeviceCounts
-    st = Stage()
-    st.t_start = t_start
-    st.dev = torch.device(getattr(args, "device", None) or "cuda:0")
-    if st.dev.type != "cuda":
-        raise RuntimeError(f"spadot_amd takes {what} on the MI355X only (device 'cuda:N'); there is no CPU path")
-    raw, path = load_marker_counts(args.data)
-    st.extras = resolve(raw) if resolve else None
-    if not getattr(args, "output_dir", None):
-        args.output_dir = os.path.dirname(path) if path else os.getcwd()
-    os.makedirs(args.output_dir, exist_ok=True)
-    st.out_dir, st.prefix = args.output_dir, getattr(args, "prefix", "") or ""
-    st.dc = DeviceCounts(raw, st.dev)
-    if not np.all(np.isfinite(st.dc.spatial)):
-        raise ValueError("the data holds spots without finite spatial coordinates")
-    st.tps, st.off = [str(t) for t in st.dc.tps], st.dc.tp_off_host
-    st.t_read = time.perf_counter()
-    st.edges = [spatial_edges(st.dc.spatial[st.rows(t)], k, st.dev) for t in range(st.dc.T)]
-    torch.cuda.synchronize(st.dev)
-    st.t_graph = time.perf_counter()
-    return st
-
-
-def timings(st, t_dev, t_end):
-    """The `timings` of a stage's result: t_dev after the device part, t_end after the files are written."""
-    return dict(read_s=st.t_read - st.t_start, graph_s=st.t_graph - st.t_read, device_s=t_dev - st.t_graph, write_s=t_end - t_dev,
-                total_s=t_end - st.t_start)

@@ -23,13 +23,13 @@ splitmix64(seed ^ (g << 32) ^ p), applied again while the value is >= n (cycle w
 
 The device counts; the host validates, takes the statistics and writes the files.  Limits: 1 <= K <= 32, at most 2147483647
 nodes and edges per graph and labelings per call."""
-import os
 import sys
 import time
 
 import numpy as np
 
-from .utils._stage_utils import edge_pair
+from .utils._stage_utils import (cuda_device, edge_pair, open_output, plot_timepoints, read_domains_table, timings,
+                                 write_timepoints)
 
 MAX_CLUSTERS = 32
 MAX_NODES = 2147483647
@@ -279,72 +279,38 @@ def neighbors(args):
     and, with matplotlib, {prefix}{tp}_nhood.png.  Returns {'tables', 'results' (per time point), 'spots', 'timepoints',
     'timings'}."""
     import pandas as pd
-    from .markers import read_domains
     from .utils import _analyze_utils
     t_start = time.perf_counter()
-    domains = getattr(args, "domains", None)
-    if domains is None or (isinstance(domains, str) and not domains):
-        raise ValueError("the neighbors stage needs the domains table of analyze (--domains)")
-    df = pd.read_csv(domains) if isinstance(domains, (str, os.PathLike)) else domains
-    for col in ("pixel_x", "pixel_y", "timepoint", "kmeans"):
-        if col not in df.columns:
-            raise ValueError(f"the domains table has no `{col}` column (expected the domains.csv that analyze writes)")
-    n = len(df)
-    if n == 0:
-        raise ValueError("the domains table is empty")
-    tp_all = np.asarray(df["timepoint"])
-    row_ids = np.asarray(df["row"]) if "row" in df.columns else np.arange(n)
-    labels = read_domains(df.assign(row=np.arange(n)), tp_all).astype(np.int64)     # the table's own order; K <= 32 per time point
-    coords = np.stack([np.asarray(df["pixel_x"], dtype=np.float64), np.asarray(df["pixel_y"], dtype=np.float64)], axis=1)
-    if not np.all(np.isfinite(coords)):
-        raise ValueError("the domains table holds spots without finite pixel_x / pixel_y")
+    tab = read_domains_table(args, "neighbors")
     k, n_perms, seed = int(getattr(args, "k", 6)), int(getattr(args, "n_perms", 1000)), int(getattr(args, "seed", 0))
     if k < 1 or n_perms < 1:
         raise ValueError(f"the neighbors stage takes k >= 1 and n_perms >= 1 (got k = {k}, n_perms = {n_perms})")
-    if not getattr(args, "output_dir", None):
-        args.output_dir = (os.path.dirname(os.path.abspath(domains)) if isinstance(domains, (str, os.PathLike))
-                           else os.getcwd())
-    os.makedirs(args.output_dir, exist_ok=True)
-    prefix = getattr(args, "prefix", "") or ""
-    device = getattr(args, "device", None) or "cuda:0"
+    out_file = open_output(args, tab.beside)
 
     import torch
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("spadot_amd counts neighbourhoods on the MI355X only (device 'cuda:N'); there is no CPU path")
-    tps = sorted(set(tp_all.tolist()))
-    masks = [tp_all == tp for tp in tps]
+    dev = cuda_device(args, "counts neighbourhoods")
+    tps, masks = tab.tps, tab.masks
     t_read = time.perf_counter()
-    edges = [spatial_edges(coords[m], k, dev) for m in masks]
-    labs = [torch.as_tensor(labels[m], device=dev) for m in masks]
-    Ks = [int(labels[m].max()) + 1 for m in masks]
+    edges = [spatial_edges(tab.coords[m], k, dev) for m in masks]
+    labs = [torch.as_tensor(tab.labels[m], device=dev) for m in masks]
     torch.cuda.synchronize(dev)
     t_graph = time.perf_counter()
-    res = nhood_enrichment(edges, labs, n_perms=n_perms, seed=seed, n_clusters=Ks)
-    same = np.empty(n, dtype=np.float64)
+    res = nhood_enrichment(edges, labs, n_perms=n_perms, seed=seed, n_clusters=tab.Ks)
+    same = np.empty(tab.n, dtype=np.float64)
     for m, (src, dst), lab in zip(masks, edges, labs):
         same[m] = same_domain_share(src, dst, lab).cpu().numpy()
     torch.cuda.synchronize(dev)
     t_dev = time.perf_counter()
 
-    tables, arrays = {}, {}
-    for tp, r in zip(tps, res):
-        tables[tp] = nhood_table(r)
-        tables[tp].to_csv(os.path.join(args.output_dir, f"{prefix}nhood_{tp}.csv"), index=False)
-        for name in MATRICES:
-            arrays[f"{tp}_{name}"] = getattr(r, name)
-    np.savez(os.path.join(args.output_dir, prefix + "nhood.npz"), timepoints=np.asarray(tps), seed=np.int64(seed), k=np.int64(k),
-             n_perms=np.int64(n_perms), **arrays)
-    spots = pd.DataFrame({"row": row_ids, "timepoint": tp_all, "kmeans": labels, "same": same}, columns=list(SPOT_COLUMNS))
-    spots.to_csv(os.path.join(args.output_dir, prefix + "nhood_spots.csv"), index=False)
-    if _analyze_utils.have_matplotlib():
-        for tp, r in zip(tps, res):
-            _analyze_utils.plot_nhood(os.path.join(args.output_dir, f"{prefix}{tp}_nhood.png"), r.zscore, tp)
-    else:
-        print("matplotlib not installed: no plots")
+    tables, arrays = write_timepoints(out_file, "nhood", tps, res, lambda t, r: nhood_table(r), MATRICES)
+    np.savez(out_file("nhood.npz"), timepoints=np.asarray(tps), seed=np.int64(seed), k=np.int64(k), n_perms=np.int64(n_perms),
+             **arrays)
+    spots = pd.DataFrame({"row": tab.row_ids, "timepoint": tab.tp_all, "kmeans": tab.labels, "same": same},
+                         columns=list(SPOT_COLUMNS))
+    spots.to_csv(out_file("nhood_spots.csv"), index=False)
+    plot_timepoints(tps, res, lambda tp, r: _analyze_utils.plot_nhood(out_file(f"{tp}_nhood.png"), r.zscore, tp))
     t_end = time.perf_counter()
-    print(f"neighbors: {n} spots of {len(tps)} time points, k = {k}, {n_perms} permutations, written to {args.output_dir}",
+    print(f"neighbors: {tab.n} spots of {len(tps)} time points, k = {k}, {n_perms} permutations, written to {args.output_dir}",
           file=sys.stderr)
     return {"tables": tables, "results": dict(zip(tps, res)), "spots": spots, "timepoints": tps,
-            "timings": dict(read_s=t_read - t_start, graph_s=t_graph - t_read, device_s=t_dev - t_graph, write_s=t_end - t_dev,
-                            total_s=t_end - t_start)}
+            "timings": timings(t_start, t_read, t_dev, t_end, t_graph)}

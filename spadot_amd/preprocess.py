@@ -37,6 +37,7 @@ from ._lib import model_lib
 from .sctransform import sctransform
 from .utils._preprocess_utils import (N_KERNELS, RawCounts, by_adjust, kernel_coordinates, load_counts, rank_genes,  # noqa: F401
                                       select_svgs, timepoint_order)
+from .utils._stage_utils import open_output
 
 DETECT_THRESHOLD = 0.01        # sctransform vst: genes with a count >= 0.01 ...
 MIN_CELLS = 5                  # ... in at least 5 spots
@@ -329,9 +330,7 @@ def preprocess(args):
     also {prefix}{stem}.h5ad, and with feature selection SVG_genes.txt and {tp}_SVG_sparkx_clustered_louvain.csv.
     Returns the result dict of preprocess_counts."""
     raw, path = load_counts(args.data)
-    if not getattr(args, "output_dir", None):
-        args.output_dir = os.path.dirname(path) if path else os.getcwd()
-    os.makedirs(args.output_dir, exist_ok=True)
+    open_output(args, path)                               # this stage has a default prefix of its own
     prefix = getattr(args, "prefix", "preprocessed_")
     prefix = "" if prefix is None else prefix
     device = getattr(args, "device", None) or "cuda:0"

@@ -49,14 +49,14 @@ statistic outside the modes of a call is not counted: NaN throughout, and withou
 Limits: K <= 32, B <= 64, S <= 9999, M <= 1048576, 256 vertices, 2147483391 spots per problem, 65535 problems per call and
 K (1 + S) <= 65535 patterns per problem."""
 import collections
-import os
 import sys
 import time
 
 import numpy as np
 
 from .pairs import MAX_BINS, counted, default_radii, ladder, mad_p, sorted_problems, thresholds
-from .utils._stage_utils import savez_pinned
+from .utils._stage_utils import (cuda_device, open_output, plot_timepoints, read_domains_table, savez_pinned, timings,
+                                 write_timepoints)
 
 MAX_SIMULATIONS = 9999
 MAX_PROBES = 1048576
@@ -335,25 +335,9 @@ def ripley_stage(args):
     (SUMMARY_COLUMNS), {prefix}ripley.npz ('{tp}_counts', '{tp}_value', '{tp}_radii', '{tp}_sizes', '{tp}_window', '{tp}_area',
     '{tp}_p_global', '{tp}_padj', plus timepoints, bins, n_sim, n_probes, seed, null, modes) and, with matplotlib,
     {prefix}{tp}_ripley.png.  Returns {'tables', 'summary', 'results' (per time point), 'timepoints', 'timings'}."""
-    import pandas as pd
-    from .markers import read_domains
     from .utils import _analyze_utils
     t_start = time.perf_counter()
-    domains = getattr(args, "domains", None)
-    if domains is None or (isinstance(domains, str) and not domains):
-        raise ValueError("the ripley stage needs the domains table of analyze (--domains)")
-    df = pd.read_csv(domains) if isinstance(domains, (str, os.PathLike)) else domains
-    for col in ("pixel_x", "pixel_y", "timepoint", "kmeans"):
-        if col not in df.columns:
-            raise ValueError(f"the domains table has no `{col}` column (expected the domains.csv that analyze writes)")
-    n = len(df)
-    if n == 0:
-        raise ValueError("the domains table is empty")
-    tp_all = np.asarray(df["timepoint"])
-    labels = read_domains(df.assign(row=np.arange(n)), tp_all).astype(np.int64)     # the table's own order; K <= 32 per time point
-    coords = np.stack([np.asarray(df["pixel_x"], dtype=np.float64), np.asarray(df["pixel_y"], dtype=np.float64)], axis=1)
-    if not np.all(np.isfinite(coords)):
-        raise ValueError("the domains table holds spots without finite pixel_x / pixel_y")
+    tab = read_domains_table(args, "ripley")
     bins, radius = int(getattr(args, "bins", 50)), getattr(args, "radius", None)
     if not 1 <= bins <= MAX_BINS:
         raise ValueError(f"the ripley stage takes 1 to {MAX_BINS} radii (got bins = {bins})")
@@ -364,46 +348,28 @@ def ripley_stage(args):
     alpha, seed = float(getattr(args, "alpha", 0.05)), int(getattr(args, "seed", 0))
     if window not in ("hull", "box"):
         raise ValueError(f"the ripley stage takes the window 'hull' or 'box' (got {window!r})")
-    if not getattr(args, "output_dir", None):
-        args.output_dir = (os.path.dirname(os.path.abspath(domains)) if isinstance(domains, (str, os.PathLike))
-                           else os.getcwd())
-    os.makedirs(args.output_dir, exist_ok=True)
-    prefix = getattr(args, "prefix", "") or ""
-    device = getattr(args, "device", None) or "cuda:0"
+    out_file = open_output(args, tab.beside)
 
     import torch
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError(NO_CPU.format("device 'cuda:N'"))
-    tps = sorted(set(tp_all.tolist()))
-    masks = [tp_all == tp for tp in tps]
-    radii = [ladder(radius, bins) if radius is not None else default_radii(coords[m], bins) for m in masks]
+    dev = cuda_device(args, "counts Ripley's functions")
+    tps, masks = tab.tps, tab.masks
+    radii = [ladder(radius, bins) if radius is not None else default_radii(tab.coords[m], bins) for m in masks]
     t_read = time.perf_counter()
-    res = ripley([torch.as_tensor(coords[m], device=dev) for m in masks], [labels[m] for m in masks], radii=radii, n_sim=n_sim,
-                 n_probes=n_probes, null=null, modes=modes, seed=seed, window=window, alpha=alpha,
-                 n_clusters=[int(labels[m].max()) + 1 for m in masks])
+    res = ripley([torch.as_tensor(tab.coords[m], device=dev) for m in masks], [tab.labels[m] for m in masks], radii=radii,
+                 n_sim=n_sim, n_probes=n_probes, null=null, modes=modes, seed=seed, window=window, alpha=alpha, n_clusters=tab.Ks)
     torch.cuda.synchronize(dev)
     t_dev = time.perf_counter()
 
-    tables = {}
     arrays = {"timepoints": np.asarray(tps), "bins": np.int64(bins), "n_sim": np.int64(n_sim), "n_probes": np.int64(n_probes),
               "seed": np.int64(seed), "null": np.asarray(null), "modes": np.asarray(",".join(modes))}
-    for tp, r in zip(tps, res):
-        tables[tp] = ripley_table(r)
-        tables[tp].to_csv(os.path.join(args.output_dir, f"{prefix}ripley_{tp}.csv"), index=False)
-        for name in ARRAYS:
-            arrays[f"{tp}_{name}"] = np.asarray(getattr(r, name))
+    tables, arrays = write_timepoints(out_file, "ripley", tps, res, lambda t, r: ripley_table(r), ARRAYS, arrays)
     summary = ripley_summary(tps, res)
-    summary.to_csv(os.path.join(args.output_dir, prefix + "ripley_summary.csv"), index=False)
-    savez_pinned(os.path.join(args.output_dir, prefix + "ripley.npz"), arrays)
-    if _analyze_utils.have_matplotlib():
-        for tp, r in zip(tps, res):
-            _analyze_utils.plot_ripley(os.path.join(args.output_dir, f"{prefix}{tp}_ripley.png"), r.radii, r.observed, r.sim_mean,
-                                       r.sim_min, r.sim_max, tp, r.pattern)
-    else:
-        print("matplotlib not installed: no plots")
+    summary.to_csv(out_file("ripley_summary.csv"), index=False)
+    savez_pinned(out_file("ripley.npz"), arrays)
+    plot_timepoints(tps, res, lambda tp, r: _analyze_utils.plot_ripley(out_file(f"{tp}_ripley.png"), r.radii, r.observed,
+                                                                      r.sim_mean, r.sim_min, r.sim_max, tp, r.pattern))
     t_end = time.perf_counter()
-    print(f"ripley: {n} spots of {len(tps)} time points, {bins} radii, {n_sim} simulations under null '{null}', written to "
+    print(f"ripley: {tab.n} spots of {len(tps)} time points, {bins} radii, {n_sim} simulations under null '{null}', written to "
           f"{args.output_dir}", file=sys.stderr)
     return {"tables": tables, "summary": summary, "results": dict(zip(tps, res)), "timepoints": tps,
-            "timings": dict(read_s=t_read - t_start, device_s=t_dev - t_read, write_s=t_end - t_dev, total_s=t_end - t_start)}
+            "timings": timings(t_start, t_read, t_dev, t_end)}

@@ -22,6 +22,8 @@ import time
 
 import numpy as np
 
+from .utils._stage_utils import cuda_device, need_domains, open_output, read_domains, timepoint_masks, timings
+
 MAX_DIM = 32
 MAX_CLUSTERS = 32
 MAX_PROBLEMS = 65535
@@ -187,13 +189,10 @@ def score(args):
     {prefix}silhouette_summary.csv (timepoint, domain, n, silhouette: the mean over every domain's spots and a row `all` per
     time point).  Returns {'samples', 'summary' (DataFrames), 'scores' (per time point), 'timepoints', 'timings'}."""
     import pandas as pd
-    from .markers import read_domains
     from .utils import _utils
     t_start = time.perf_counter()
     adata, path = _utils.load_data(args.data)
-    domains = getattr(args, "domains", None)
-    if domains is None or (isinstance(domains, str) and not domains):
-        raise ValueError("the score stage needs the domains table of analyze (--domains)")
+    domains = need_domains(args, "score")
     X = np.asarray(adata.X.toarray() if hasattr(adata.X, "toarray") else adata.X)
     tp_all = np.asarray(adata.obs["timepoint"])
     n = X.shape[0]
@@ -207,18 +206,11 @@ def score(args):
     labels = read_domains(_positions(df, row_ids, n), tp_all).astype(np.int64)
     if not 1 <= X.shape[1] <= MAX_DIM:
         raise ValueError(f"the latent has {X.shape[1]} dimensions; the device silhouette supports 1 to {MAX_DIM}")
-    if not getattr(args, "output_dir", None):
-        args.output_dir = os.path.dirname(path) if path else os.getcwd()
-    os.makedirs(args.output_dir, exist_ok=True)
-    prefix = getattr(args, "prefix", "") or ""
-    device = getattr(args, "device", None) or "cuda:0"
+    out_file = open_output(args, path)
 
     import torch
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("spadot_amd scores silhouettes on the MI355X only (device 'cuda:N'); there is no CPU path")
-    tps = sorted(set(tp_all.tolist()))
-    masks = [tp_all == tp for tp in tps]
+    dev = cuda_device(args, "scores silhouettes")
+    tps, masks = timepoint_masks(tp_all)
     t_read = time.perf_counter()
     Xs = [torch.as_tensor(np.ascontiguousarray(X[m]), device=dev) for m in masks]
     labs = [labels[m] for m in masks]
@@ -241,9 +233,9 @@ def score(args):
                             "a": cols["a"], "b": cols["b"], "nearest": nearest, "silhouette": cols["silhouette"]},
                            columns=list(SAMPLE_COLUMNS))
     summary = pd.DataFrame(summary, columns=list(SUMMARY_COLUMNS))
-    samples.to_csv(os.path.join(args.output_dir, prefix + "silhouette.csv"), index=False)
-    summary.to_csv(os.path.join(args.output_dir, prefix + "silhouette_summary.csv"), index=False)
+    samples.to_csv(out_file("silhouette.csv"), index=False)
+    summary.to_csv(out_file("silhouette_summary.csv"), index=False)
     t_end = time.perf_counter()
     print(f"score: {n} spots of {len(tps)} time points written to {args.output_dir}", file=sys.stderr)
     return {"samples": samples, "summary": summary, "scores": scores, "timepoints": tps,
-            "timings": dict(read_s=t_read - t_start, device_s=t_dev - t_read, write_s=t_end - t_dev, total_s=t_end - t_start)}
+            "timings": timings(t_start, t_read, t_dev, t_end)}

@@ -29,15 +29,15 @@ form: the variance is not distinguishable from zero; scipy returns NaN there).  
 point, fate) over the genes with a nonzero among the valid spots (the others: r = 0, p = padj = 1).
 
 The device sums; the host does the plumbing (row matching, centring, the t distribution, BH, ordering and the files)."""
-import os
 import sys
 import time
 
 import numpy as np
 
 from ._call import launched, ptr as _p, stream as _stream
-from .markers import TARGET_SUM, bh_adjust, load_marker_counts
+from .markers import TARGET_SUM, bh_adjust
 from .utils._preprocess_utils import RawCounts, load_counts
+from .utils._stage_utils import align_rows, load_marker_counts, open_output, top_setting
 
 MAX_COLUMNS = 1024             # columns of W in one call (the kernel keeps 16 per lane)
 MAX_ROWS = 2 ** 31 - 1
@@ -277,30 +277,14 @@ def read_lineage(path, timepoint):
     for key in ("X", "rows", "timepoint", "names"):
         if key not in z.files:
             raise ValueError(f"{path} has no `{key}` array (expected a trajectories.npz or fates.npz of analyze --lineage)")
-    tp = np.asarray(timepoint)
-    n = tp.shape[0]
     X, row, ztp = np.asarray(z["X"]), np.asarray(z["rows"]), np.asarray(z["timepoint"])
-    if row.dtype.kind not in "iu":
-        raise ValueError(f"the `rows` of {path} must hold integer row numbers of the data")
-    if X.ndim != 2 or X.shape[0] != row.shape[0] or ztp.shape[0] != row.shape[0] or len(z["names"]) != X.shape[1]:
+    shapes = X.ndim == 2 and X.shape[0] == row.shape[0] and ztp.shape[0] == row.shape[0] and len(z["names"]) == X.shape[1]
+    if row.dtype.kind in "iu" and not shapes:                # rows that are no integers are refused first, by align_rows
         raise ValueError(f"{path}: X of shape {X.shape} against {row.shape[0]} rows, {ztp.shape[0]} time point entries and "
                          f"{len(z['names'])} names")
-    row = row.astype(np.int64)
-    if row.size and (row.min() < 0 or row.max() >= n):
-        raise ValueError(f"{path} names row {int(row.max() if row.max() >= n else row.min())}: the data has rows 0 .. {n - 1}")
-    seen = np.bincount(row, minlength=n)
-    if np.any(seen > 1):
-        raise ValueError(f"row {int(np.flatnonzero(seen > 1)[0])} appears more than once in {path} "
-                         f"({int((seen > 1).sum())} duplicate rows)")
-    if np.any(seen == 0):
-        raise ValueError(f"row {int(np.flatnonzero(seen == 0)[0])} of the data is missing from {path} "
-                         f"({int((seen == 0).sum())} missing rows)")
-    bad = np.flatnonzero(ztp.astype(str) != tp[row].astype(str))
-    if bad.size:
-        r = int(row[bad[0]])
-        raise ValueError(f"time point mismatch at row {r}: {path} says {str(ztp[bad[0]])!r}, the data says {str(tp[r])!r} "
-                         f"({bad.size} rows differ)")
-    out = np.empty((n, X.shape[1]), dtype=np.float64)
+    row = align_rows(row, ztp, timepoint, f"the `rows` of {path}", path, f"appears more than once in {path}",
+                     f"is missing from {path}", show=lambda v: repr(str(v)))
+    out = np.empty((row.shape[0], X.shape[1]), dtype=np.float64)
     out[row] = X
     return out, np.asarray(z["names"]).astype(str)
 
@@ -348,38 +332,32 @@ def trends(args):
     if not traj and not fates:
         raise ValueError("the trends stage needs trajectories.npz and / or fates.npz of analyze --lineage (--trajectories, "
                          "--fates)")
-    top = getattr(args, "top", 100)
-    top = 100 if top is None else int(top)
-    if top < 0:
-        raise ValueError(f"top must be 0 (all genes) or a positive count, not {top}")
+    top = top_setting(args, 100, least=0)
     raw, path = load_marker_counts(args.data)
     tp = raw.obs["timepoint"]
     W = read_lineage(traj, tp) if traj else None
     F = read_lineage(fates, tp) if fates else None
-    if not getattr(args, "output_dir", None):
-        args.output_dir = os.path.dirname(path) if path else os.getcwd()
-    os.makedirs(args.output_dir, exist_ok=True)
-    prefix = getattr(args, "prefix", "") or ""
+    out_file = open_output(args, path)
     device = getattr(args, "device", None) or "cuda:0"
     out, timings = {}, {}
-    if W is not None:
-        res = gene_trends(raw, W[0], names=W[1], device=device)
+
+    def save(res, keys, archive, names_key):
+        """The archive of one result; its arrays and names go to `out`."""
         common = dict(names=np.asarray(res["names"]).astype(str), genes=np.asarray(res["genes"]).astype(str),
                       timepoints=np.asarray([str(t) for t in res["timepoints"]]))
-        np.savez(os.path.join(args.output_dir, prefix + "trends.npz"), **{k: res[k] for k in TREND_KEYS}, **common)
-        trends_table(res, top).to_csv(os.path.join(args.output_dir, prefix + "trends_top.csv"), index=False)
-        out.update({k: res[k] for k in TREND_KEYS}, trajectory_names=common["names"], genes=common["genes"],
-                   timepoints=common["timepoints"])
+        np.savez(out_file(archive), **{k: res[k] for k in keys}, **common)
+        out.update({k: res[k] for k in keys}, **{names_key: common["names"]}, genes=common["genes"], timepoints=common["timepoints"])
+        return common["timepoints"]
+
+    if W is not None:
+        res = gene_trends(raw, W[0], names=W[1], device=device)
+        save(res, TREND_KEYS, "trends.npz", "trajectory_names")
+        trends_table(res, top).to_csv(out_file("trends_top.csv"), index=False)
         timings["trends"] = res["timings"]
     if F is not None:
         res = fate_drivers(raw, F[0], names=F[1], device=device)
-        common = dict(names=np.asarray(res["names"]).astype(str), genes=np.asarray(res["genes"]).astype(str),
-                      timepoints=np.asarray([str(t) for t in res["timepoints"]]))
-        np.savez(os.path.join(args.output_dir, prefix + "drivers.npz"), **{k: res[k] for k in DRIVER_KEYS}, **common)
-        for t, name in enumerate(common["timepoints"]):
-            drivers_table(res, t, top).to_csv(os.path.join(args.output_dir, f"{prefix}drivers_{name}.csv"), index=False)
-        out.update({k: res[k] for k in DRIVER_KEYS}, fate_names=common["names"], genes=common["genes"],
-                   timepoints=common["timepoints"])
+        for t, name in enumerate(save(res, DRIVER_KEYS, "drivers.npz", "fate_names")):
+            drivers_table(res, t, top).to_csv(out_file(f"drivers_{name}.csv"), index=False)
         timings["drivers"] = res["timings"]
     out["timings"] = timings
     print(f"trends: {len(out['genes'])} genes x {len(out['timepoints'])} time points written to {args.output_dir}",
