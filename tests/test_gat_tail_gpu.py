@@ -101,15 +101,22 @@ def test_tail_bf16_at_the_benchmarked_layer_shape_vs_oracle_and_vs_the_map_first
     """8 000 source rows x 2048 channels, 512 seeds, ~31 incoming edges each, H = 4, C = 512 in bf16: the aggregate-first
     result against the fp64 oracle (bf16-level tolerances, written here) and against the map-first path on the same inputs
     (dense map over all rows + per-edge kernels); both paths must sit equally close to the oracle."""
+    n, rows, k, H, C, K = 8000, 512, 30, 4, 512, 2048
+    _bf16_vs_oracle_and_map_first(rows, H, C, *_problem(n, rows, k, H, C, K, seed=77, hub=False))
+
+
+def _bf16_vs_oracle_and_map_first(rows, H, C, ei, x, W, a_s, a_d, bias, gsel, pad=0):
     from spadot_amd import ops
     from spadot_amd.graph import build_batch_graph
-    n, rows, k, H, C, K = 8000, 512, 30, 4, 512, 2048
-    ei, x, W, a_s, a_d, bias, gsel = _problem(n, rows, k, H, C, K, seed=77, hub=False)
+    n = x.shape[0]
     # bf16-representable inputs, so that the comparison sees the kernels' arithmetic and not the input rounding
     x = T(x).to(torch.bfloat16).double().numpy()
     W = T(W).to(torch.bfloat16).double().numpy()
     out_o, grads_o = _oracle(ei, x, W, a_s, a_d, bias, gsel, H, rows)
-    out_t, grads_t = _tail(ops, ei, x, W, a_s, a_d, bias, gsel, H, C, rows, torch.bfloat16)
+    out_t, grads_t = _tail(ops, ei, x, W, a_s, a_d, bias, gsel, H, C, rows, torch.bfloat16, pad=pad)
+    if pad:
+        assert np.all(grads_t[0][n:] == 0.0), "pad rows of the input must get a zero gradient"
+        grads_t[0] = grads_t[0][:n]
     # the path it replaces
     g = build_batch_graph(ei, n, DEV, seeds=rows).seed_graph
     xd = T(x).to(DEV, torch.bfloat16).requires_grad_(True)
@@ -133,3 +140,45 @@ def test_tail_bf16_at_the_benchmarked_layer_shape_vs_oracle_and_vs_the_map_first
         rt, rm, ct = rel(t_, o_), rel(m_, o_), cos(t_, o_)
         print("%-8s rel-L2: tail %.3e, map-first %.3e, cos(tail, oracle) %.6f" % (name, rt, rm, ct))
         assert ct >= 0.999 and rt <= 0.05 and rt <= 2.0 * rm + 5e-3, name
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The source backward's UNSTAGED branch (k_tail_src_bwd: a block of 8 source rows with more than 128 out-edges), which the random
+# graphs above never reach -- a source there has about one edge into the few targets.  gat_cases.tail_hub() has two sources that
+# send to every one of its 163 targets (asserted on the host in tests/test_gat_ref_cpu.py), a block that straddles n_tgt, and
+# with 5 pad rows a last block that straddles both n and rows_out.
+
+def _hub_problem(H, C, K, seed):
+    import gat_cases
+    c = gat_cases.tail_hub()
+    rng = np.random.default_rng(seed)
+    x = rng.normal(size=(c.n, K)) * 0.7
+    W = rng.normal(size=(H * C, K)) / np.sqrt(K)
+    a_s = rng.normal(size=(1, H, C)) * 0.3
+    a_d = rng.normal(size=(1, H, C)) * 0.3
+    bias = rng.normal(size=C) * 0.1
+    gsel = rng.normal(size=(c.n_tgt, C))
+    return c, (torch.as_tensor(c.edge_index()), x, W, a_s, a_d, bias, gsel)
+
+
+# K = 64: 8 of the 256 threads hold columns, K % 32 == 0 (bf16: the matrix-core logit / edge kernels); K = 40: K % 32 != 0
+@pytest.mark.parametrize("K", [64, 40])
+def test_tail_unstaged_source_blocks_fp32_match_the_fp64_oracle(K):
+    from spadot_amd import ops
+    H, C = 4, 16
+    c, prob = _hub_problem(H, C, K, seed=K)
+    out_o, grads_o = _oracle(*prob, H, c.n_tgt)
+    out_d, grads_d = _tail(ops, *prob, H, C, c.n_tgt, torch.float32, pad=c.marks["pad"])
+    np.testing.assert_allclose(out_d, out_o, rtol=1e-4, atol=2e-5)
+    for name, d, o in zip(("x", "W", "att_src", "att_dst", "bias"), grads_d, grads_o):
+        if name == "x":
+            assert np.all(d[c.n:] == 0.0), "pad rows of the input must get a zero gradient"
+            d = d[:c.n]
+        np.testing.assert_allclose(d, o, rtol=2e-3, atol=2e-4 * np.abs(o).max(), err_msg=name)
+
+
+@pytest.mark.parametrize("K", [64, 40])
+def test_tail_unstaged_source_blocks_bf16_vs_oracle_and_vs_the_map_first_path(K):
+    H, C = 4, 16
+    c, prob = _hub_problem(H, C, K, seed=K + 1)
+    _bf16_vs_oracle_and_map_first(c.n_tgt, H, C, *prob, pad=c.marks["pad"])

@@ -215,3 +215,92 @@ def test_gemm_nn_matches_fp32_reference(M, N, K):
     err = (outs[0].float() - ref).abs()
     assert bool((err <= 2.0 ** -8 * ref.abs() + 1e-5 * mag + 1e-30).all()), float(err.max())
     assert torch.equal(outs[0], outs[1])
+
+
+SLOPE = 0.01
+_SUBTILE_EDGES = (31, 32, 159, 160, 319, 320)      # last / first rows of a 32-row sub-tile, of a wave's 160 rows, of a 320-row panel
+
+
+def _mask_for(M, N, ldm, seed):
+    """bf16 [M x N] view (row stride ldm) of random values of both signs, with +0.0 and -0.0 scattered over it, and every row at
+    a sub-tile boundary (and row M - 1) wholly non-positive with both zeros in it."""
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    buf = torch.randn((M, ldm), device=DEV, generator=g).bfloat16()
+    msk = buf[:, :N]
+    flat = torch.randperm(M * N, device=DEV, generator=g)
+    nz = max(2, (M * N) // 50)
+    rows, cols = flat[:2 * nz] // N, flat[:2 * nz] % N
+    msk[rows[:nz], cols[:nz]] = 0.0
+    msk[rows[nz:], cols[nz:]] = -0.0
+    for r in _SUBTILE_EDGES + (M - 1,):
+        if r < M:
+            msk[r] = -msk[r].abs()
+            msk[r, 0::5] = 0.0
+            msk[r, 2::5] = -0.0
+    assert bool((msk > 0).any()) or M <= 2
+    assert bool((msk.view(torch.int16) == 0).any()) and bool((msk.view(torch.int16) == -32768).any())          # +0.0 and -0.0
+    return msk
+
+
+def _nn(lib, name, A, B, C, M, *tail):
+    K, N = B.shape
+    rc = getattr(lib, name)(A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), C.data_ptr(), C.stride(0), M, N, K, *tail,
+                            torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return rc
+
+
+@pytest.mark.parametrize("M,N,K", [
+    (1, 256, 64),            # a single row: every mask prefetch is clamped to row 0
+    (33, 256, 64),           # one sub-tile plus one row
+    (321, 512, 192),         # second panel of one row: every prefetch of that panel clamps to M - 1
+    (479, 256, 128),         # the second panel ends inside sub-tile 4 of wave-row 1
+    (2600, 2048, 2048),      # the shape of the handoff in tests/test_gat_handoff_gpu.py
+])
+@pytest.mark.parametrize("wide_mask", [False, True])
+def test_gemm_nn_masked_is_the_unmasked_result_scaled_where_the_mask_is_not_positive(M, N, K, wide_mask):
+    """spadot_gemm_nn_bf16_masked (the LeakyReLU' of the layer below in the input-gradient GEMM's epilogue) against
+    spadot_gemm_nn_bf16 on the same operands, which test_gemm_nn_matches_fp32_reference holds to its fp32 bound.  The epilogue
+    scales the already-rounded bf16 patch and packs it again with pack2 = a plain float -> __bf16 conversion, which rounds to
+    nearest even like torch's .bfloat16(): so EVERY element is asserted bit for bit --
+    bf16(float(C_unmasked) * slope) where mask <= 0 (+0.0, -0.0 and negative alike), C_unmasked elsewhere.
+    Rows >= M of an over-allocated C keep their fill; two launches give the same bits."""
+    from spadot_amd import _lib
+    lib = _lib.model_lib()
+    g = torch.Generator(device=DEV).manual_seed(M * 5 + K)
+    A = (torch.randn((M, K), device=DEV, generator=g) * 0.7).bfloat16()
+    B = (torch.randn((K, N), device=DEV, generator=g) * 0.1).bfloat16()
+    msk = _mask_for(M, N, N + 24 if wide_mask else N, seed=M + N)
+    plain = torch.full((M, N), float("nan"), device=DEV, dtype=torch.bfloat16)
+    assert _nn(lib, "spadot_gemm_nn_bf16", A, B, plain, M) == 0
+    assert torch.isfinite(plain.float()).all()
+    slope = torch.tensor(SLOPE, dtype=torch.float32, device=DEV)
+    want = torch.where(msk > 0, plain, (plain.float() * slope).bfloat16())
+    outs = []
+    for _ in range(2):
+        C = torch.full((M + 7, N), float("nan"), device=DEV, dtype=torch.bfloat16)
+        assert _nn(lib, "spadot_gemm_nn_bf16_masked", A, B, C, M, msk.data_ptr(), msk.stride(0), SLOPE) == 0
+        outs.append(C)
+    C = outs[0]
+    bad = C[:M].view(torch.int16) != want.view(torch.int16)
+    assert not bool(bad.any()), (int(bad.sum()), torch.nonzero(bad)[:8].tolist())
+    assert torch.isnan(C[M:].float()).all()
+    assert torch.equal(outs[0].view(torch.int16), outs[1].view(torch.int16))
+
+
+def test_gemm_nn_masked_refuses_a_mask_it_cannot_read():
+    from spadot_amd import _lib
+    lib = _lib.model_lib()
+    M, N, K = 64, 256, 64
+    A = torch.zeros((M, K), device=DEV, dtype=torch.bfloat16)
+    B = torch.zeros((K, N), device=DEV, dtype=torch.bfloat16)
+    C = torch.zeros((M, N), device=DEV, dtype=torch.bfloat16)
+    mbuf = torch.ones((M + 1, N + 8), device=DEV, dtype=torch.bfloat16)
+    st = torch.cuda.current_stream().cuda_stream
+    args = (A.data_ptr(), K, B.data_ptr(), N, C.data_ptr(), N, M, N, K)
+    assert lib.spadot_gemm_nn_bf16_masked(*args, mbuf.data_ptr(), N + 8, SLOPE, st) == 0
+    assert lib.spadot_gemm_nn_bf16_masked(*args, None, N, SLOPE, st) == -22                            # no mask
+    assert lib.spadot_gemm_nn_bf16_masked(*args, mbuf.data_ptr(), N - 8, SLOPE, st) == -22              # ldm < N
+    assert lib.spadot_gemm_nn_bf16_masked(*args, mbuf.data_ptr(), N + 4, SLOPE, st) == -22              # ldm % 8 != 0
+    assert lib.spadot_gemm_nn_bf16_masked(*args, mbuf.data_ptr() + 2, N + 8, SLOPE, st) == -22          # off 16-byte alignment
+    torch.cuda.synchronize()
