@@ -26,6 +26,7 @@
  *   spadot_ripley_*          no counterpart in the reference: the pair, nearest-neighbour and empty-space counts of squidpy's gr.ripley
  *   spadot_local_lag         no counterpart in the reference: the neighbour sums and permutation counts of esda's Moran_Local
  *   spadot_cross_*           no counterpart in the reference: the cross sums of a bivariate Moran's I between genes (esda's Moran_BV)
+ *   spadot_corr_sums         no counterpart in the reference: the band sums of a spatial correlogram (spdep's sp.correlogram)
  *   spadot_autocorr_sums     no counterpart in the reference: the edge sums of squidpy's gr.spatial_autocorr (Moran's I, Geary's C)
  *   spadot_ligrec_*          no counterpart in the reference: the per-domain sums and comparison counts of squidpy's gr.ligrec
  */
@@ -972,6 +973,42 @@ int spadot_cross_dense(const int *rowptr, const int *col, const long long *colpt
 int spadot_cross_sums(const double *Z, const double *Y, long long zrows, int GP, const long long *desc_host,
                       const long long *desc_dev, int T, int ng, int observed, long long first, long long P, long long seed,
                       double *M, void *stream);
+
+/* ---------------------------------------------------------------- spatial correlogram (csrc/correlogram.hip)
+ * The sums behind Moran's I by distance band of every (time point, selected gene, labeling); the definition is restated in numpy
+ * in tests/correlogram_ref.py.  A time point is n spots and B squared thresholds r2[0] < .. < r2[B-1]; band b holds the ordered
+ * pairs (i, j), i != j, with r2[b-1] < d2(i, j) <= r2[b] (r2[-1] below 0: coincident spots are in band 0; pairs beyond r2[B-1] are
+ * in no band), d2 the unfused squared distance of spadot_cooccur_counts.  cnt_b(i): the partners of spot i in band b.  With
+ * x_i = Z[zoff + pi_l(i), j], Z the image of spadot_cross_dense and pi_l the identity (l = 0 if observed) or the permutation
+ * first + .. of spadot_nhood_counts under (seed, graph id, p, n):
+ *   W[t, b] = sum_i cnt_b(i)      S2c[t, b] = sum_i cnt_b(i)^2                                   (int64, exact; see below)
+ *   N[t, j, l, b] = sum over the pairs of band b of x_i x_j      Q[t, j, l, b] = sum_i cnt_b(i) x_i^2      (fp64)
+ * xy: fp64 [sum n, 2], per time point its spots in ANY order that keeps near spots near (the Morton order of graph.morton_key),
+ * the time points back to back; order: int32 [sum n], per position the original index 0 .. n-1 of its spot (a permutation: the
+ * caller's to refuse; the kernel clamps).  desc [T, 6] int64, once in host memory (checked here) and once on the device:
+ *   0 first spot in xy (checked)   1 n   2 B   3 graph id of the permutation keys   4 zoff   5 the blocks of 256 spots of the
+ *   time points before (checked)
+ * r2 [T, 16] fp64, once on the host (checked here) and once on the device: the B squared thresholds, finite, >= 0 and strictly
+ * increasing, then +inf in every padded place.
+ * One 256-thread workgroup per (256 positions, labeling and chunk of cs genes, time point); tiles of 256 spots stream through LDS
+ * and a tile whose bounding box lies further than r2[B-1] from that of the query block is skipped where cull = 1 (no bit of any
+ * output changes: DESIGN 7o).  A thread adds its partners in ascending position, the workgroup its threads in a fixed order into
+ * a partial per (block, column, band) in scratch, and a second launch adds the partials in ascending block order: the bits of one
+ * (time point, gene, labeling, band) depend on nothing else of the call, neither on cs, cull nor the split over `first`.  No
+ * floating-point atomics; W and S2c are 64-bit integer atomics from the workgroups of column chunk 0.
+ * S2c is exact while sum_i cnt_b(i)^2 < 2^63 (always for n <= 2097152); a larger time point with a dense band can wrap it, and
+ * is not refused.
+ * cs: 2 or 4 (0: the default, 2).  scratch: fp64 [scratch_doubles] with scratch_doubles >= 4 blocks + 2 blocks (observed + P) ng
+ * B_max, blocks = sum ceil(n / 256).  skipped: NULL or int64 [1], the (query block, tile) pairs that were culled.
+ * out: W, S2c int64 [T, B_max]; N, Q fp64 [T, ng, observed + P, B_max]; written completely (zeros in the bands >= B).
+ * Return -22 for null or inconsistent arguments (GP other than ng rounded up to 16, a scratch buffer that is too small, rows of a
+ * time point outside zrows, padding other than +inf among them) and -7, before any launch, outside the limits: 1 <= B <= B_max <=
+ * 16, ng <= 4096, 1 <= n <= 2147483391, T <= 65535 (gridDim.z), (observed + P) ceil(ng / cs) <= 65535 (gridDim.y), first + P <=
+ * 2^32, graph id <= 2147483647, a threshold that is negative, not finite or not above the one before. */
+int spadot_corr_sums(const double *xy, const int *order, const double *Z, long long zrows, int GP, const long long *desc_host,
+                     const long long *desc_dev, const double *r2_host, const double *r2_dev, int T, int ng, int B_max, int observed,
+                     long long first, long long P, long long seed, int cull, int cs, double *scratch, long long scratch_doubles,
+                     long long *W, long long *S2c, double *N, double *Q, long long *skipped, void *stream);
 
 /* ---------------------------------------------------------------- trends stage (csrc/trends.hip)
  * The log-normalised counts of every time point, transposed, times a dense row-major fp64 W[n, C] (rows in the permuted order of

@@ -20,6 +20,8 @@
                                  [--threshold 0.1] [--top 100] [--device cuda:0]
     python -m spadot_amd ripley --domains CSV [-o DIR] [--prefix P] [--bins 50] [--radius R] [--n_sim 99] [--n_probes 1000]
                                 [--null labels|csr] [--mode L,G,F] [--window hull|box] [--alpha 0.05] [--seed 0] [--device cuda:0]
+    python -m spadot_amd correlogram -i COUNTS [-o DIR] [--prefix P] [--genes A,B | FILE] [--top 50] [--bins 12 | --radii r1,r2,..]
+                                     [--n_perms 0] [--alpha 0.05] [--seed 0] [--device cuda:0]
 
 `preprocess` runs SPARK-X feature selection and the scaling on the device (spadot_amd.preprocess).  The balancing rule's gene
 clusters come from K-means by default; `--gene_clusters louvain` clusters SCTransform Pearson residuals with Louvain as the
@@ -59,7 +61,9 @@ its domain) and F (the distance from random probe points to the domain) over the
 envelope of `--n_sim` simulated patterns of the same size -- by default the domain's label dealt out at random over the spots
 (`--null labels`, the right null on a lattice of spots), or points uniform in the window (`--null csr`, squidpy's) -- with
 pointwise p-values, a global envelope test per domain and a verdict `clustered`, `dispersed` or `random` (spadot_amd.ripley,
-DESIGN 7n)."""
+DESIGN 7n).  `correlogram` reads the counts of `autocorr` and asks HOW FAR the structure of a gene reaches: Moran's I and the
+semivariance of every selected gene over the pairs of spots in successive distance bands, and the range, the distance at which the
+autocorrelation stops (spadot_amd.correlogram)."""
 import argparse
 import os
 import sys
@@ -305,6 +309,35 @@ def build_parser():
                     help="Pairs listed per time point in the pair tables, by descending |R|; 0 lists all. Default: 0")
     mo.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
 
+    cg = sub.add_parser("correlogram", help="How far the spatial structure of a gene reaches: Moran's I and the semivariance of "
+                                            "every selected gene over the pairs of spots in successive distance bands, and "
+                                            "the range at which the autocorrelation stops.")
+    cg.add_argument("-i", "--data", dest="data", type=str, required=True,
+                    help="The counts: the .npz written by preprocess (its raw counts of the selected genes), or raw counts as "
+                         "preprocess reads them (.npz or .h5ad).")
+    cg.add_argument("-o", "--output_dir", dest="output_dir", type=str,
+                    help="Output directory. Default: the same as where the data locates.")
+    cg.add_argument("--prefix", dest="prefix", type=str, default="", help="Prefix for the correlogram tables. Default: ''")
+    cg.add_argument("--genes", dest="genes", type=str,
+                    help="The genes to test: a comma-separated list of names, or a file with one name per line. Default: the "
+                         "--top genes by Moran's I of every time point.")
+    cg.add_argument("--top", dest="top", type=int, default=50,
+                    help="Without --genes: the genes taken per time point by descending Moran's I (their union is tested). "
+                         "Default: 50")
+    cg.add_argument("--bins", dest="bins", type=int, default=12, help="Distance bands per time point, 1 to 16. Default: 12")
+    cg.add_argument("--radii", dest="radii", type=str,
+                    help="The upper ends of the bands, in the units of the coordinates: a comma-separated increasing list of 1 "
+                         "to 16 radii, for every time point. Default: --bins equal bands up to a quarter of the diagonal of "
+                         "the time point's bounding box.")
+    cg.add_argument("--n_perms", dest="n_perms", type=int, default=0,
+                    help="Random relabelings of the spots behind z_sim and p_sim; 0 tests against the analytic null alone. "
+                         "Default: 0")
+    cg.add_argument("--alpha", dest="alpha", type=float, default=0.05,
+                    help="The range of a gene ends at the first band whose adjusted p-value is above this (or whose Moran's I "
+                         "is not above its expectation). Default: 0.05")
+    cg.add_argument("--seed", dest="seed", type=int, default=0, help="Seed of the relabelings. Default: 0")
+    cg.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
+
     lr = sub.add_parser("ligrec", help="Ligand-receptor tests between the spatial domains of every time point: the mean expression "
                                        "of every pair between every two domains, with a permutation null.")
     lr.add_argument("-i", "--data", dest="data", type=str, required=True,
@@ -428,6 +461,13 @@ def main(argv=None):
             sys.exit(2)
         from .modules import modules
         modules(args)
+    elif args.cmd_choice == "correlogram":
+        if not _exists(args.data):
+            print(f"SpaDOT correlogram: the counts do not exist: {args.data}. Please make sure they are correctly specified.",
+                  file=sys.stderr)
+            sys.exit(2)
+        from .correlogram import correlogram_stage
+        correlogram_stage(args)
     elif args.cmd_choice == "ligrec":
         for what, path in (("counts", args.data), ("domains table", args.domains), ("interactions table", args.interactions)):
             if not _exists(path):

@@ -1,4 +1,4 @@
-"""The launches of the analysis stages (silhouette, gmm, neighbors, cooccurrence, autocorr, ligrec, hotspots, modules, ripley) in
+"""The launches of the analysis stages (silhouette, gmm, neighbors, cooccurrence, autocorr, ligrec, hotspots, modules, ripley, correlogram) in
 libspadot_model.so (include/spadot_model.h).  A *_check refuses, before any launch, what the library would refuse or cannot see (ranges that only a
 reduction on the device knows: one host round trip); a *_launch hands over what the check returned.  CPU tensors raise."""
 import ctypes
@@ -929,6 +929,143 @@ def cross_sums(Z, Y, desc, ng, observed, first, P, seed=0, out=None):
     seed.  Returns M, an fp64 device tensor [T, observed + P, ng, ng] (out: the tensor to write into).  ValueError, before any
     launch, outside the limits; RuntimeError for a CPU tensor."""
     return cross_launch(Z, Y, cross_check(Z, Y, desc, ng, observed, first, P), ng, observed, first, P, seed, out)
+
+
+CORR_DESC = 6
+CORR_MAX_B = 16                    # bands of a time point: the thresholds are padded to this with +inf
+CORR_MAX_G = CROSS_MAX_G           # selected genes of a call, as the images of cross_dense
+CORR_MAX_N = COOCCUR_MAX_N
+CORR_MAX_T = 65535                 # time points of a call (gridDim.z)
+CORR_MAX_Y = 65535                 # labelings x chunks of genes of a call (gridDim.y)
+CORR_MAX_GID = COOCCUR_MAX_G
+CORR_CS = 2                        # the library's default (DESIGN 7o)
+CORR_LIMITS = ("1 <= B <= 16 thresholds that are finite, >= 0 and strictly increasing, 1 <= G <= 4096 selected genes, 1 <= n <= "
+               "2147483391 spots per time point, at most 65535 time points and (observed + P) ceil(G / cs) <= 65535 labelings x "
+               "chunks of genes per call, permutation indices below 2^32, graph ids in 0 .. 2147483647, cs in (2, 4)")
+
+
+def corr_layout(sizes):
+    """(boff int64 [T], blocks): the blocks of 256 spots ahead of every time point, and of the call."""
+    b = np.concatenate([[0], np.cumsum((np.asarray(sizes, dtype=np.int64) + 255) // 256)]).astype(np.int64)
+    return b[:-1], int(b[-1])
+
+
+def corr_scratch_doubles(blocks, ng, L, B_max):
+    """The doubles of the scratch buffer of a call, as the library computes it: the boxes, then the partials."""
+    return int(blocks) * 4 + 2 * int(blocks) * int(L) * int(ng) * int(B_max)
+
+
+def corr_check(xy, order, Z, desc, r2, ng, observed, first, P, cs=None):
+    """The refusals of corr_sums, before any launch: the limits from the descriptor, the thresholds and the shapes, then, by
+    reductions on the device (one host round trip), that `order` holds a permutation of 0 .. n-1 per time point and that the
+    coordinates are finite.  r2: [T] sequences of squared thresholds, or the array [T, 16] padded with +inf.  Returns (desc
+    int64 [T, 6], r2 fp64 [T, 16] padded with +inf, B_max, observed as 0 / 1, first, P); ValueError otherwise."""
+    need_cuda(xy, order, Z)
+    desc = _host_desc(desc, CORR_DESC, "time point")
+    T, ng, cs = int(desc.shape[0]), int(ng), int(cs or 0)
+    if not 1 <= ng <= CORR_MAX_G:
+        raise ValueError(f"spadot_corr_sums takes 1 to {CORR_MAX_G} selected genes (got {ng})")
+    if cs not in (0, 2, 4):
+        raise ValueError(f"spadot_corr_sums takes cs in (2, 4) (got {cs})")
+    if T > CORR_MAX_T:
+        raise ValueError(f"the call holds {T} time points: spadot_corr_sums takes at most {CORR_MAX_T} (the grid of one launch)")
+    if len(r2) != T:
+        raise ValueError(f"the call holds {T} time points and {len(r2)} sets of thresholds")
+    observed, first, P = labelings("corr_sums", observed, first, P)
+    if (observed + P) * -(-ng // (cs or CORR_CS)) > CORR_MAX_Y:
+        raise ValueError(f"the call holds {observed + P} labelings x {-(-ng // (cs or CORR_CS))} chunks of genes: spadot_corr_sums "
+                         f"takes at most {CORR_MAX_Y} (the grid of one launch; split the labelings or the genes)")
+    pad = np.full((T, CORR_MAX_B), np.inf, dtype=np.float64)
+    off = blocks = need = B_max = 0
+    for t, (o, n, B, gid, zoff, boff) in enumerate(desc.tolist()):
+        if not 1 <= B <= CORR_MAX_B:
+            raise ValueError(f"time point {t} has {B} thresholds: spadot_corr_sums takes 1 to {CORR_MAX_B}")
+        if not 1 <= n <= CORR_MAX_N:
+            raise ValueError(f"time point {t} has {n} spots: spadot_corr_sums takes 1 to {CORR_MAX_N} (int32 positions)")
+        if not 0 <= gid <= CORR_MAX_GID:
+            raise ValueError(f"time point {t} has the graph id {gid}: spadot_corr_sums takes 0 to {CORR_MAX_GID}")
+        if o != off or boff != blocks or zoff < 0:
+            raise ValueError(f"time point {t}: inconsistent descriptor {desc[t].tolist()}")
+        th = np.asarray(r2[t], dtype=np.float64).reshape(-1)
+        if th.shape[0] == CORR_MAX_B and np.all(th[B:] == np.inf):
+            th = th[:B]
+        if th.shape[0] != B:
+            raise ValueError(f"time point {t} has {th.shape[0]} thresholds and its descriptor says {B}")
+        if not np.all(np.isfinite(th)) or np.any(th < 0) or np.any(np.diff(th) <= 0):
+            raise ValueError(f"the squared thresholds of time point {t} must be finite, >= 0 and strictly increasing")
+        pad[t, :B] = th
+        off, blocks, need, B_max = off + n, blocks + (n + 255) // 256, max(need, zoff + (n + 3) // 4 * 4), max(B_max, B)
+    if xy.dtype != torch.float64 or xy.dim() != 2 or xy.shape[1] != 2 or not xy.is_contiguous() or xy.shape[0] != off:
+        raise ValueError(f"xy must be a contiguous fp64 [{off}, 2] tensor (got {tuple(xy.shape)} {xy.dtype})")
+    if order.dtype != torch.int32 or order.dim() != 1 or not order.is_contiguous() or order.shape[0] != off:
+        raise ValueError(f"order must be a contiguous int32 tensor of {off} positions (got {tuple(order.shape)} {order.dtype})")
+    _cross_image(Z, "Z", int(Z.shape[0]) if Z.dim() == 2 else -1, cross_padded(ng))
+    if Z.shape[0] < need:
+        raise ValueError(f"Z holds {int(Z.shape[0])} rows: the time points need {need}")
+    stats = []
+    for o, n, *_rest in desc.tolist():
+        seen = torch.sort(order[o:o + n].long()).values
+        stats += [(seen != torch.arange(n, dtype=torch.int64, device=order.device)).any().long(),
+                  torch.isfinite(xy[o:o + n]).all().long()]
+    stats = torch.stack(stats).cpu().numpy().reshape(T, 2)                  # the one host round trip ahead of the launch
+    for t in range(T):
+        if stats[t, 0]:
+            raise ValueError(f"the order of time point {t} is not a permutation of 0 .. {int(desc[t, 1]) - 1}")
+        if not stats[t, 1]:
+            raise ValueError(f"time point {t} holds coordinates that are not finite")
+    return desc, pad, B_max, observed, first, P
+
+
+def corr_launch(xy, order, Z, checked, ng, seed=0, cull=True, cs=None, out=None, scratch=None, skipped=None, desc_dev=None,
+                r2_dev=None):
+    """The launch of corr_sums for what corr_check has returned (the library checks the descriptor and the thresholds again, on
+    the host).  Returns (W, S2c, N, Q)."""
+    desc, r2, B_max, observed, first, P = checked
+    need_cuda(xy, order, Z, scratch, skipped, desc_dev, r2_dev, *(out or ()))
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    r2 = np.ascontiguousarray(r2, dtype=np.float64)
+    T, ng, L, cs, dev = int(desc.shape[0]), int(ng), int(observed) + int(P), int(cs or 0), xy.device
+    if cs not in (0, 2, 4):                                               # the library's refusal, ahead of the call
+        launched(-7, "spadot_corr_sums", CORR_LIMITS)
+    if out is None:
+        out = (torch.empty((T, B_max), dtype=torch.int64, device=dev), torch.empty((T, B_max), dtype=torch.int64, device=dev),
+               torch.empty((T, ng, L, B_max), dtype=torch.float64, device=dev),
+               torch.empty((T, ng, L, B_max), dtype=torch.float64, device=dev))
+    elif (len(out) != 4 or any(not o.is_contiguous() for o in out)
+          or any(o.dtype != torch.int64 or o.numel() != T * B_max for o in out[:2])
+          or any(o.dtype != torch.float64 or o.numel() != T * ng * L * B_max for o in out[2:])):
+        raise ValueError(f"out must be two contiguous int64 tensors of {T} x {B_max} values and two contiguous float64 tensors of "
+                         f"{T} x {ng} x {L} x {B_max}")
+    need = corr_scratch_doubles(int(((desc[:, 1] + 255) // 256).sum()), ng, L, B_max)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.float64, device=dev)
+    elif scratch.dtype != torch.float64 or not scratch.is_contiguous() or scratch.numel() < need:
+        raise ValueError(f"scratch must be a contiguous float64 tensor of at least {need} values")
+    if skipped is not None and (skipped.dtype != torch.int64 or skipped.numel() != 1):
+        raise ValueError("skipped must be an int64 tensor of one value")
+    if desc_dev is None:
+        desc_dev = torch.as_tensor(desc, device=dev)
+    if r2_dev is None:
+        r2_dev = torch.as_tensor(r2, device=dev)
+    rc = model_lib().spadot_corr_sums(_p(xy), _p(order), _p(Z), int(Z.shape[0]), cross_padded(ng), _host(desc), _p(desc_dev),
+                                      _host(r2), _p(r2_dev), T, ng, B_max, int(observed), int(first), int(P), _signed64(seed),
+                                      int(bool(cull)), cs, _p(scratch), int(scratch.numel()), _p(out[0]), _p(out[1]), _p(out[2]),
+                                      _p(out[3]), _p(skipped), _stream())
+    launched(rc, "spadot_corr_sums", CORR_LIMITS)
+    return out
+
+
+def corr_sums(xy, order, Z, desc, r2, ng, observed, first, P, seed=0, cull=True, cs=None, out=None, scratch=None, skipped=None):
+    """The band sums behind the spatial correlogram of every (time point, selected gene, labeling) (include/spadot_model.h:
+    spadot_corr_sums).  xy: fp64 [sum n, 2] device tensor, per time point its spots in Morton order, the time points back to back;
+    order int32 [sum n]: the original index of every position; Z: the image of cross_dense; desc: int64 [T, 6] on the host as
+    the header lays it out; r2[t]: the squared thresholds of time point t.  Labelings: the identity (observed) and the
+    permutations first .. first + P - 1 under seed.  cull: skip the tiles out of reach (the same bits either way); skipped: an
+    int64 device tensor of one value that receives the number of skipped tiles.  Returns (W int64 [T, B_max], S2c int64
+    [T, B_max], N fp64 [T, ng, observed + P, B_max], Q the same) (out: the four to write into).  ValueError, before any launch,
+    outside the limits; RuntimeError for a CPU tensor."""
+    checked = corr_check(xy, order, Z, desc, r2, ng, observed, first, P, cs)
+    return corr_launch(xy, order, Z, checked, ng, seed, cull, cs, out, scratch, skipped)
 
 
 RIPLEY_MAX_K = COOCCUR_MAX_K

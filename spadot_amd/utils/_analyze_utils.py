@@ -284,6 +284,23 @@ def plot_ripley(path, radii, observed, sim_mean, sim_min, sim_max, timepoint, pa
     fig.savefig(path)
 
 
+def plot_correlogram(path, mids, I, expected, names, timepoint):
+    """{prefix}{tp}_correlogram.png: Moran's I of the leading genes (the rows of I [genes, bands]) against the middle of the
+    distance band, with its expectation under no autocorrelation as a dashed line."""
+    fig = _figure((7.5, 5))
+    ax = fig.add_subplot(1, 1, 1)
+    for row, name in zip(np.asarray(I, dtype=np.float64), names):
+        ax.plot(mids, row, marker="o", markersize=3, linewidth=1.2, label=str(name))
+    ax.axhline(expected, color="0.4", linewidth=0.8, linestyle="--")
+    ax.set_xlabel("distance")
+    ax.set_ylabel("Moran's I")
+    ax.set_title("Correlogram, time point: {}".format(timepoint))
+    if len(names):
+        ax.legend(fontsize=7, ncol=2)
+    fig.tight_layout()
+    fig.savefig(path)
+
+
 def transition_min_prob(table):
     """Element-wise minimum of the column-normalised and the row-normalised transition table (_analyze_utils.py:184-194)."""
     t = np.asarray(table, dtype=np.float64)
