@@ -1010,6 +1010,53 @@ int spadot_corr_sums(const double *xy, const int *order, const double *Z, long l
                      long long first, long long P, long long seed, int cull, int cs, double *scratch, long long scratch_doubles,
                      long long *W, long long *S2c, double *N, double *Q, long long *skipped, void *stream);
 
+/* ---------------------------------------------------------------- embed stage (csrc/embed.hip)
+ * t-SNE of P problems (sets of n points in d dimensions, fp64) with sklearn's objective and optimiser, Barnes-Hut's sparse input
+ * affinities and EXACT repulsion over all pairs in fp64.  The problems lie back to back in every array; prob [P, 10] int64, once in
+ * host memory (checked here) and once on the device:
+ *   0 first point (checked)   1 n   2 k = min(n - 1, floor(3 u))   3 first entry of the neighbour lists, sum n k before (checked)
+ *   4 S, the slices of the partner range, 1 .. 65535   5 sum n S before (checked)   6 first entry of rowptr, the points
+ *   before plus the problems before (checked)   7 first stored entry of the CSR (checked)   8 sum ceil(n / 256) before (checked)
+ *   9 stored entries of the problem
+ * spadot_latent_knn reads the columns 0 .. 3, spadot_tsne_affinities too; spadot_tsne_steps reads all.
+ *
+ * spadot_latent_knn: per point the k nearest OTHER points by (squared distance, index) ascending; idx int32 and d2 fp64
+ * [sum n k], row i of a problem at column 3 + i k.  The squared distance is sum_c (x_ic - x_jc)^2, c ascending, UNFUSED: every
+ * subtraction, product and addition is rounded once.  Self is left out by index; a duplicate of a point is its neighbour at
+ * distance 0.  One 64-thread workgroup per 64 queries, a query's list in LDS as [slot][lane] (12 k 64 bytes).
+ *
+ * spadot_tsne_affinities: per row, with e_j = d2_j - min_j d2_j, p_j = exp(-(beta e_j)), s = sum p_j and H = log s + beta
+ * (sum e_j p_j) / s: from beta = 1, 200 steps (H > log u: beta goes up, doubled while it has no upper bracket, else to the middle
+ * of the bracket; otherwise down, halved or to the middle), no early stop; then cond_j = p_j / s at the last beta.  A row whose e
+ * are all 0 is uniform and reports beta = 0.  perp [P] fp64 on the host (checked) and on the device; cond fp64 [sum n k], beta
+ * fp64 [sum n].  One wavefront per row.
+ *
+ * spadot_tsne_steps queues the iterations it0 .. it0 + steps - 1 without a host synchronisation.  Iteration `it` reads Y from
+ * (it odd ? Y1 : Y0) and writes the other buffer; with eps = exaggeration and mu = 0.5 while it < early, else eps = 1, mu = 0.8:
+ *   q_ij = 1 / (1 + |y_i - y_j|^2) (IEEE division, the distance unfused), j != i by a select;  z_i = sum_j q_ij,  r_i = sum_j
+ *   q_ij^2 (y_i - y_j), j ascending inside each of the S slices of whole 256-tiles (slice s: the tiles floor(s T / S) ..
+ *   floor((s + 1) T / S) - 1 of T = ceil(n / 256); a slice without tiles adds exact zeros), the slices in their order;
+ *   Z = sum_i z_i: a fixed tree per block of 256 points, the blocks ascending;  a_i = sum over row i of the CSR, in stored order,
+ *   of ((eps P_ij) q_ij) (y_i - y_j);  g_i = 4 (a_i - r_i / Z);  per component: gain += 0.2 where update g < 0, else gain *= 0.8,
+ *   at least 0.01;  update = mu update - lr (gain g);  y += update  (unfused: numpy on `grad` repeats them bit for bit);
+ *   kl[p, it] = sum over the stored entries with P_ij > 0 of P_ij (log P_ij - log q_ij) + log Z (unexaggerated P).
+ * rowptr int64 [sum (n + 1)], per problem ascending from 0; col int32 in 0 .. n-1 (the caller's to refuse: the kernel clamps),
+ * val fp64.  Y0, Y1, upd, gains, grad, att fp64 [sum n, 2]; lr fp64 [P] on the device; part fp64 [sum n S, 3] and blk fp64
+ * [sum ceil(n / 256), 2]: scratch; zr fp64 [sum n, 3] (z_i, r_i), att (a_i), grad (g_i) and Z fp64 [P] hold the last iteration's;
+ * kl fp64 [P, kl_stride].  two: 1 gives a thread two query points (the same bits).  No atomics.
+ *
+ * All three return -22 for null or inconsistent arguments and -7, before any launch, outside the limits: 1 <= d <= 32, at most
+ * 65535 problems, 2 <= n <= 2147483135, 1 <= k <= min(n - 1, 150), 2 <= u <= 50, n >= u + 2, 1 <= S <= 65535,
+ * exaggeration >= 1. */
+int spadot_latent_knn(const double *x, int d, int P, const long long *prob_host, const long long *prob_dev, int *idx, double *d2,
+                      void *stream);
+int spadot_tsne_affinities(const double *d2, int P, const long long *prob_host, const long long *prob_dev, const double *perp_host,
+                           const double *perp_dev, double *cond, double *beta, void *stream);
+int spadot_tsne_steps(const long long *prob_host, const long long *prob_dev, int P, const long long *rowptr, const int *col,
+                      const double *val, double *Y0, double *Y1, double *upd, double *gains, const double *lr, double *part,
+                      double *zr, double *att, double *blk, double *grad, double *Z, double *kl, long long kl_stride, long long it0,
+                      int steps, long long early, double exaggeration, int two, void *stream);
+
 /* ---------------------------------------------------------------- trends stage (csrc/trends.hip)
  * The log-normalised counts of every time point, transposed, times a dense row-major fp64 W[n, C] (rows in the permuted order of
  * the CSC arrays), as three weighted moments in one pass over the stored entries.  Same CSC layout as the preprocess and markers

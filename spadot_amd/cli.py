@@ -22,6 +22,8 @@
                                 [--null labels|csr] [--mode L,G,F] [--window hull|box] [--alpha 0.05] [--seed 0] [--device cuda:0]
     python -m spadot_amd correlogram -i COUNTS [-o DIR] [--prefix P] [--genes A,B | FILE] [--top 50] [--bins 12 | --radii r1,r2,..]
                                      [--n_perms 0] [--alpha 0.05] [--seed 0] [--device cuda:0]
+    python -m spadot_amd embed   -i LATENT [--domains CSV] [-o DIR] [--prefix P] [--perplexity 30] [--n_iter 1000] [--early 250]
+                                 [--learning_rate LR] [--per_timepoint] [--device cuda:0]
 
 `preprocess` runs SPARK-X feature selection and the scaling on the device (spadot_amd.preprocess).  The balancing rule's gene
 clusters come from K-means by default; `--gene_clusters louvain` clusters SCTransform Pearson residuals with Louvain as the
@@ -63,7 +65,10 @@ envelope of `--n_sim` simulated patterns of the same size -- by default the doma
 pointwise p-values, a global envelope test per domain and a verdict `clustered`, `dispersed` or `random` (spadot_amd.ripley,
 DESIGN 7n).  `correlogram` reads the counts of `autocorr` and asks HOW FAR the structure of a gene reaches: Moran's I and the
 semivariance of every selected gene over the pairs of spots in successive distance bands, and the range, the distance at which the
-autocorrelation stops (spadot_amd.correlogram)."""
+autocorrelation stops (spadot_amd.correlogram).  `embed` reads the latents and draws the map a user looks at first: a
+t-SNE of all time points together (or of every time point on its own with `--per_timepoint`) with sklearn's objective and
+optimiser and the repulsion summed exactly over all pairs in fp64, bitwise repeatable; with `--domains` the table and the plot
+carry the domain of every spot (spadot_amd.embed)."""
 import argparse
 import os
 import sys
@@ -338,6 +343,27 @@ def build_parser():
     cg.add_argument("--seed", dest="seed", type=int, default=0, help="Seed of the relabelings. Default: 0")
     cg.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
 
+    em = sub.add_parser("embed", help="A two-dimensional t-SNE map of the latent space, all time points together or one map per "
+                                      "time point: exact repulsion in fp64 on the device, bitwise repeatable.")
+    em.add_argument("-i", "--data", dest="data", type=str, required=True,
+                    help="The latent representations: latent.npz (or latent.h5ad, needs anndata) written by train.")
+    em.add_argument("--domains", dest="domains", type=str,
+                    help="The domains.csv written by analyze (row, timepoint, kmeans): adds the kmeans column and the second panel "
+                         "of the plot.")
+    em.add_argument("-o", "--output_dir", dest="output_dir", type=str,
+                    help="Output directory. Default: the same as where the data locates.")
+    em.add_argument("--prefix", dest="prefix", type=str, default="", help="Prefix for the embedding files. Default: ''")
+    em.add_argument("--perplexity", dest="perplexity", type=float, default=30.0,
+                    help="Perplexity of the input affinities, 2 to 50; every embedded set needs perplexity + 2 spots. Default: 30")
+    em.add_argument("--n_iter", dest="n_iter", type=int, default=1000, help="Iterations; there is no early stop. Default: 1000")
+    em.add_argument("--early", dest="early", type=int, default=250,
+                    help="Iterations of the early-exaggeration phase (exaggeration 12, momentum 0.5). Default: 250")
+    em.add_argument("--learning_rate", dest="learning_rate", type=float,
+                    help="Learning rate. Default: max(n / 12 / 4, 50) for a set of n spots, as sklearn's 'auto'.")
+    em.add_argument("--per_timepoint", dest="per_timepoint", default=False, action="store_true",
+                    help="One embedding per time point (one launch for all of them) instead of one joint embedding.")
+    em.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
+
     lr = sub.add_parser("ligrec", help="Ligand-receptor tests between the spatial domains of every time point: the mean expression "
                                        "of every pair between every two domains, with a permutation null.")
     lr.add_argument("-i", "--data", dest="data", type=str, required=True,
@@ -468,6 +494,15 @@ def main(argv=None):
             sys.exit(2)
         from .correlogram import correlogram_stage
         correlogram_stage(args)
+    elif args.cmd_choice == "embed":
+        named = [("domains table", args.domains)] if args.domains else []
+        for what, path in [("latent representations", args.data)] + named:
+            if not _exists(path):
+                print(f"SpaDOT embed: the {what} does not exist: {path}. Please make sure it is correctly specified.",
+                      file=sys.stderr)
+                sys.exit(2)
+        from .embed import embed
+        embed(args)
     elif args.cmd_choice == "ligrec":
         for what, path in (("counts", args.data), ("domains table", args.domains), ("interactions table", args.interactions)):
             if not _exists(path):

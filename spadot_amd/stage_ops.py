@@ -1,4 +1,5 @@
-"""The launches of the analysis stages (silhouette, gmm, neighbors, cooccurrence, autocorr, ligrec, hotspots, modules, ripley, correlogram) in
+"""The launches of the analysis stages (silhouette, gmm, neighbors, cooccurrence, autocorr, ligrec, hotspots, modules, ripley, correlogram,
+embed) in
 libspadot_model.so (include/spadot_model.h).  A *_check refuses, before any launch, what the library would refuse or cannot see (ranges that only a
 reduction on the device knows: one host round trip); a *_launch hands over what the check returned.  CPU tensors raise."""
 import ctypes
@@ -1207,3 +1208,167 @@ def ripley_points(vertices, cum, seed, g, stream, count, device=None, out=None):
         launched(model_lib().spadot_ripley_points(_host(v), _p(vd), _host(c), _p(cd), int(v.shape[0]), _signed64(seed), g, stream,
                                                   count, _p(out), _stream()), "spadot_ripley_points", RIPLEY_LIMITS)
     return out
+
+
+EMBED_DESC = 10
+EMBED_MAX_D = 32
+EMBED_MAX_K = 150                  # floor(3 * 50)
+EMBED_MAX_P = 65535                # problems of a call (gridDim.y / gridDim.z)
+EMBED_MAX_S = 65535                # slices of a problem (gridDim.y)
+EMBED_MAX_N = 2147483135           # points of a problem: int32 positions of a 512-wide block
+EMBED_TILE = 256
+EMBED_WORKGROUPS = 1024            # the slice rule aims at this many repulsion workgroups: four per CU of an MI355X
+EMBED_SCRATCH_BYTES = 1 << 30
+EMBED_LIMITS = ("1 <= d <= 32, at most 65535 problems, 2 <= perplexity <= 50, perplexity + 2 <= n <= 2147483135 points per problem, "
+                "k = min(n - 1, floor(3 perplexity)) neighbours, 1 <= slices <= 65535, exaggeration >= 1")
+
+
+def embed_neighbors(n, perplexity):
+    """k = min(n - 1, floor(3 perplexity)): the neighbours behind the affinities of a problem of n points."""
+    return min(int(n) - 1, int(np.floor(3.0 * float(perplexity))))
+
+
+def embed_slices(n):
+    """The slices of the partner range of a problem of n points: a function of n alone, so that the bits of a problem do not depend
+    on what else a launch holds.  ceil(1024 / tiles) slices of whole tiles, at most one per tile: 6 at 50 000 points (1176
+    workgroups on the 256 CUs of an MI355X), 26 at 10 000."""
+    tiles = -(-int(n) // EMBED_TILE)
+    return max(1, min(tiles, -(-EMBED_WORKGROUPS // tiles)))
+
+
+def embed_table(sizes, perplexity, slices=None, nnz=None):
+    """The problem table of the embed entries, int64 [P, 10] on the host as the header lays it out, and the perplexities fp64 [P].
+    perplexity: one number or one per problem; slices: None (embed_slices), one number or one per problem; nnz: the stored
+    entries of every problem's CSR (None before it exists).  ValueError outside the limits."""
+    sizes = [int(n) for n in sizes]
+    P = len(sizes)
+    if not 1 <= P <= EMBED_MAX_P:
+        raise ValueError(f"one call embeds 1 to {EMBED_MAX_P} problems (got {P})")
+    perp = np.broadcast_to(np.asarray(perplexity, dtype=np.float64), (P,)).copy()
+    per = [None] * P if slices is None else np.broadcast_to(np.asarray(slices, dtype=np.int64), (P,)).tolist()
+    nnz = [0] * P if nnz is None else [int(v) for v in nnz]
+    desc = np.zeros((P, EMBED_DESC), dtype=np.int64)
+    off = koff = soff = eoff = boff = 0
+    for p, (n, u) in enumerate(zip(sizes, perp.tolist())):
+        if not 2.0 <= u <= 50.0:
+            raise ValueError(f"problem {p} has the perplexity {u}: the device t-SNE takes 2 to 50")
+        if not u + 2.0 <= n <= EMBED_MAX_N:
+            raise ValueError(f"problem {p} has {n} points: a perplexity of {u} needs at least {int(np.ceil(u + 2.0))}, and the "
+                             f"device t-SNE takes at most {EMBED_MAX_N}")
+        tiles = -(-n // EMBED_TILE)
+        S = embed_slices(n) if per[p] is None else int(per[p])
+        if not 1 <= S <= EMBED_MAX_S:                   # more slices than tiles: the surplus ones hold no tile and add exact zeros
+            raise ValueError(f"problem {p} takes 1 to {EMBED_MAX_S} slices of the partner range (got {S})")
+        k = embed_neighbors(n, u)
+        desc[p] = (off, n, k, koff, S, soff, off + p, eoff, boff, nnz[p])
+        off, koff, soff, eoff, boff = off + n, koff + n * k, soff + n * S, eoff + nnz[p], boff + tiles
+    if 24 * soff > EMBED_SCRATCH_BYTES:
+        raise ValueError(f"the partial sums of the slices would take {24 * soff} bytes of scratch: more than 1 GiB "
+                         f"({EMBED_SCRATCH_BYTES}); give fewer slices or fewer problems per call")
+    return desc, perp
+
+
+def embed_check(X, desc):
+    """The refusals that the points decide, before any launch: X a contiguous fp64 [sum n, d] device tensor with 1 <= d <= 32 and
+    finite values (one reduction on the device, one host round trip)."""
+    need_cuda(X)
+    total = int(desc[-1, 0] + desc[-1, 1])
+    if X.dtype != torch.float64 or X.dim() != 2 or not X.is_contiguous() or X.shape[0] != total:
+        raise ValueError(f"X must be a contiguous fp64 [{total}, d] tensor (got {tuple(X.shape)} {X.dtype})")
+    d = int(X.shape[1])
+    if not 1 <= d <= EMBED_MAX_D:
+        raise ValueError(f"the device t-SNE supports data of 1 to {EMBED_MAX_D} dimensions (got {d})")
+    if not bool(torch.isfinite(X).all().cpu()):                              # the one host round trip ahead of the launch
+        raise ValueError("the points hold values that are not finite")
+    return d
+
+
+def latent_knn_launch(X, desc, desc_dev=None, out=None):
+    """The k nearest other points of every point of P problems in ONE launch (include/spadot_model.h: spadot_latent_knn), for what
+    embed_table and embed_check have passed.  Returns (idx int32, d2 fp64), both [sum n k]: row i of problem p at desc[p, 3] + i k."""
+    need_cuda(X, desc_dev, *(out or ()))
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    P, total = int(desc.shape[0]), int(desc[-1, 3] + desc[-1, 1] * desc[-1, 2])
+    if desc_dev is None:
+        desc_dev = torch.as_tensor(desc, device=X.device)
+    idx, d2 = out if out is not None else (torch.empty(total, dtype=torch.int32, device=X.device),
+                                           torch.empty(total, dtype=torch.float64, device=X.device))
+    _typed((idx, torch.int32, "idx"), (d2, torch.float64, "d2"))
+    if idx.numel() != total or d2.numel() != total:
+        raise ValueError(f"idx and d2 must hold {total} values")
+    launched(model_lib().spadot_latent_knn(_p(X), int(X.shape[1]), P, _host(desc), _p(desc_dev), _p(idx), _p(d2), _stream()),
+             "spadot_latent_knn", EMBED_LIMITS, f": d = {int(X.shape[1])}, {P} problems")
+    return idx, d2
+
+
+def tsne_affinities_launch(d2, desc, perp, desc_dev=None):
+    """The conditional affinities of every row of P problems in ONE launch (spadot_tsne_affinities).  d2: what latent_knn_launch
+    returned; perp: fp64 [P] on the host.  Returns (cond fp64 [sum n k], beta fp64 [sum n])."""
+    need_cuda(d2, desc_dev)
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    perp = np.ascontiguousarray(perp, dtype=np.float64)
+    P, rows = int(desc.shape[0]), int(desc[-1, 0] + desc[-1, 1])
+    _typed((d2, torch.float64, "d2"))
+    if d2.numel() != int(desc[-1, 3] + desc[-1, 1] * desc[-1, 2]) or perp.shape != (P,):
+        raise ValueError(f"d2 must hold the neighbour lists of the {P} problems and perp one perplexity per problem")
+    if desc_dev is None:
+        desc_dev = torch.as_tensor(desc, device=d2.device)
+    perp_dev = torch.as_tensor(perp, device=d2.device)
+    cond, beta = torch.empty_like(d2), torch.empty(rows, dtype=torch.float64, device=d2.device)
+    launched(model_lib().spadot_tsne_affinities(_p(d2), P, _host(desc), _p(desc_dev), _host(perp), _p(perp_dev), _p(cond), _p(beta),
+                                                _stream()), "spadot_tsne_affinities", EMBED_LIMITS)
+    return cond, beta
+
+
+def tsne_csr_check(desc, rowptr, col, val):
+    """The refusals of tsne_steps_launch that the joint affinities decide, before any launch: per problem a rowptr that ascends
+    from 0 to its stored entries and columns in 0 .. n-1 (reductions on the device, one host round trip)."""
+    need_cuda(rowptr, col, val)
+    _typed((rowptr, torch.int64, "rowptr"), (col, torch.int32, "col"), (val, torch.float64, "val"))
+    P, nnz = int(desc.shape[0]), int(desc[:, 9].sum())
+    if rowptr.numel() != int(desc[-1, 6] + desc[-1, 1] + 1) or col.numel() != nnz or val.numel() != nnz:
+        raise ValueError(f"rowptr must hold n + 1 entries per problem, col and val the {nnz} stored entries of the table")
+    zero = torch.zeros((), dtype=torch.int64, device=col.device)
+    stats = []
+    for _off, n, _k, _koff, _S, _soff, roff, eoff, _boff, E in desc.tolist():
+        rp = rowptr[roff:roff + n + 1]
+        lo, hi = torch.aminmax(col[eoff:eoff + E]) if E > 0 else (zero, zero)
+        stats += [lo.long(), hi.long(), rp[0], rp[-1], (rp[1:] < rp[:-1]).any().long()]
+    stats = torch.stack(stats).cpu().numpy().reshape(P, 5)                   # the one host round trip ahead of the launch
+    for p in range(P):
+        n, E = int(desc[p, 1]), int(desc[p, 9])
+        if E > 0 and (stats[p, 0] < 0 or stats[p, 1] >= n):
+            raise ValueError(f"problem {p} has the columns {int(stats[p, 0])} .. {int(stats[p, 1])} in col: they must lie in 0 .. "
+                             f"{n - 1}")
+        if stats[p, 2] != 0 or stats[p, 3] != E or stats[p, 4]:
+            raise ValueError(f"the rowptr of problem {p} must ascend from 0 to its {E} stored entries (it runs from "
+                             f"{int(stats[p, 2])} to {int(stats[p, 3])})")
+
+
+def tsne_state(desc, n_iter, device):
+    """The buffers of tsne_steps_launch for a table: Y0, Y1, upd, gains, grad, att fp64 [sum n, 2] (gains ones, the rest zeros), zr
+    [sum n, 3], part [sum n S, 3], blk [sum ceil(n / 256), 2], Z [P], kl [P, n_iter] (NaN), lr [P] (zeros: the caller's to set)."""
+    N, P = int(desc[-1, 0] + desc[-1, 1]), int(desc.shape[0])
+    rows = int(desc[-1, 5] + desc[-1, 1] * desc[-1, 4])
+    blocks = int(desc[-1, 8]) + -(-int(desc[-1, 1]) // EMBED_TILE)
+    z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=device)  # noqa: E731
+    return dict(Y0=z(N, 2), Y1=z(N, 2), upd=z(N, 2), gains=torch.ones((N, 2), dtype=torch.float64, device=device), grad=z(N, 2),
+                att=z(N, 2), zr=z(N, 3), part=z(rows, 3), blk=z(blocks, 2), Z=z(P), lr=z(P),
+                kl=torch.full((P, max(int(n_iter), 1)), float("nan"), dtype=torch.float64, device=device))
+
+
+def tsne_steps_launch(desc, desc_dev, rowptr, col, val, state, it0, steps, early, exaggeration=12.0, two=False):
+    """Queues the iterations it0 .. it0 + steps - 1 of P problems (spadot_tsne_steps) on the buffers of tsne_state, for a table
+    and a CSR that embed_table and tsne_csr_check have passed.  Iteration `it` reads Y0 where it is even and Y1 where it is odd,
+    and writes the other.  No host synchronisation."""
+    need_cuda(desc_dev, rowptr, col, val, *state.values())
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    it0, steps, early = int(it0), int(steps), int(early)
+    if steps < 0 or it0 < 0 or early < 0 or it0 + steps > int(state["kl"].shape[1]):
+        raise ValueError(f"the iterations {it0} .. {it0 + steps - 1} do not fit the {int(state['kl'].shape[1])} of the run")
+    s = state
+    rc = model_lib().spadot_tsne_steps(_host(desc), _p(desc_dev), int(desc.shape[0]), _p(rowptr), _p(col), _p(val), _p(s["Y0"]),
+                                       _p(s["Y1"]), _p(s["upd"]), _p(s["gains"]), _p(s["lr"]), _p(s["part"]), _p(s["zr"]),
+                                       _p(s["att"]), _p(s["blk"]), _p(s["grad"]), _p(s["Z"]), _p(s["kl"]), int(s["kl"].shape[1]), it0,
+                                       steps, early, float(exaggeration), int(bool(two)), _stream())
+    launched(rc, "spadot_tsne_steps", EMBED_LIMITS)

@@ -301,6 +301,31 @@ def plot_correlogram(path, mids, I, expected, names, timepoint):
     fig.savefig(path)
 
 
+def plot_embedding(path, Y, timepoint, labels=None):
+    """{prefix}embedding.png: the t-SNE map of the latents in two panels, coloured by time point and by domain (the second panel
+    says so where no domains table was given)."""
+    import matplotlib
+    fig = _figure((11, 5))
+    cmap = matplotlib.colormaps["tab10"]
+    Y = np.asarray(Y, dtype=np.float64)
+    for pos, (title, values) in enumerate((("time point", timepoint), ("kmeans", labels))):
+        ax = fig.add_subplot(1, 2, pos + 1)
+        if values is None:
+            ax.scatter(Y[:, 0], Y[:, 1], s=4, color="0.6", linewidths=0)
+            ax.set_title("no domains table given")
+        else:
+            values = np.asarray(values)
+            for i, c in enumerate(sorted(set(values.tolist()))):
+                m = values == c
+                ax.scatter(Y[m, 0], Y[m, 1], s=4, color=cmap(i % 10), label=str(c), linewidths=0)
+            ax.legend(title=title, fontsize=7, markerscale=2)
+            ax.set_title("by {}".format(title))
+        ax.set_xlabel("tsne_1")
+        ax.set_ylabel("tsne_2")
+    fig.tight_layout()
+    fig.savefig(path)
+
+
 def transition_min_prob(table):
     """Element-wise minimum of the column-normalised and the row-normalised transition table (_analyze_utils.py:184-194)."""
     t = np.asarray(table, dtype=np.float64)
