@@ -27,6 +27,7 @@
  *   spadot_local_lag         no counterpart in the reference: the neighbour sums and permutation counts of esda's Moran_Local
  *   spadot_cross_*           no counterpart in the reference: the cross sums of a bivariate Moran's I between genes (esda's Moran_BV)
  *   spadot_corr_sums         no counterpart in the reference: the band sums of a spatial correlogram (spdep's sp.correlogram)
+ *   spadot_sepal_steps       no counterpart in the reference: the diffusion steps and the entropy stop of squidpy's gr.sepal, on the graph
  *   spadot_autocorr_sums     no counterpart in the reference: the edge sums of squidpy's gr.spatial_autocorr (Moran's I, Geary's C)
  *   spadot_ligrec_*          no counterpart in the reference: the per-domain sums and comparison counts of squidpy's gr.ligrec
  */
@@ -1056,6 +1057,45 @@ int spadot_tsne_steps(const long long *prob_host, const long long *prob_dev, int
                       const double *val, double *Y0, double *Y1, double *upd, double *gains, const double *lr, double *part,
                       double *zr, double *att, double *blk, double *grad, double *Z, double *kl, long long kl_stride, long long it0,
                       int steps, long long early, double exaggeration, int two, void *stream);
+
+/* ---------------------------------------------------------------- sepal stage (csrc/sepal.hip)
+ * The diffusion time of every (time point, selected gene) on the spatial graph; the definition is restated in numpy in
+ * tests/sepal_ref.py.  Time point t is a SYMMETRIC CSR over its n spots (rowptr: int32 [n + 1] ascending from 0 to M, the T arrays
+ * back to back; col: int32 [M], back to back: for row i first the targets of i's own edges, then the sources of the edges that end
+ * in i, so that an edge in both directions counts twice; M = 2 E), the rows row0 .. row0 + n - 1 of the CSC matrix of
+ * spadot_local_lag and a rate a = rate[t] = dt n / M (fp64, formed by the caller).  Item (t, j), j = 0 .. ng-1, is gene genes[j] in
+ * time point t, number t ng + j.  Its image c is fp64 [n]: at first the fp32 values of the stored entries widened, 0 elsewhere.
+ * One step, Jacobi, every operation rounded once (no fused multiply-add), deg_i the length of row i:
+ *   s_i = ((0 + c_j1) + c_j2) + ..  over row i in row order     l_i = s_i - deg_i c_i     c'_i = c_i + a l_i, 0 where that is < 0
+ * The entropy of an image, over the spots with c_i > 0:  S = sum c_i, Q = sum c_i log c_i, H = (log S - Q / S) / n, both sums in a
+ * fixed order that depends on n alone (csrc/sepal.hip's header).  The image has the bits of numpy after any number of steps; H is
+ * bit-reproducible (an item alone or in a batch, either path, any split over launches) and within rounding of any other order.
+ * State per item, on the device, updated in place:
+ *   image [items, stride] fp64: the image in the first n places of a row; stride >= max n + (the largest n of the time points
+ *   whose image does not fit in LDS, 0 if all fit), the place behind max n being the second slab of that path; image_doubles: its size
+ *   H_prev fp64, iterations int32, done int32 [items]: the entropy after the last step, the steps taken, and 0 running, 1 stopped
+ *   by the rule, 2 degenerate (no positive value, n < 2 or M = 0: H_prev and H0 are NaN and no step is ever run)
+ *   H0 fp64 [items]: the entropy of the first image, written with init = 1
+ * init = 1: the image is built from the CSC column and H0, H_prev, iterations = 0 and done are written first; init = 0: the state
+ * of an earlier launch is read.  Every item that is not done then takes min(steps, n_iter - iterations) further steps; with stop =
+ * 1 it ends behind the first step t with |H^t - H^(t-1)| <= thresh (done = 1).  trace: NULL or fp64 [items, trace_len]: H after
+ * step number it goes to column it < trace_len, H0 to column 0.
+ * One 1024-thread workgroup per item, all items in ONE launch; no host round trip per step, no atomics, no workgroup waits for
+ * another.  The image lives in LDS where 512 + 8 n <= lds_limit (at most 98816, n <= 12288: what the registers of the workgroup
+ * hold between the two barriers of a step; larger values mean 98816), otherwise in the item's row of `image`.
+ * desc [T, 8] int64 as for spadot_local_lag (column 2 holds M, column 4 is not read), once on the host (checked here) and once on
+ * the device; rate once on the host (checked) and once on the device.
+ * Return -22 for null, negative or inconsistent arguments (an image that is too small among them) and -7, before any launch,
+ * outside the limits: 1 <= steps, n_iter <= 2147483647, thresh >= 0 and finite, 0 < a and finite where M > 0, 1 <= n <=
+ * 2147483647, M, nnz and row0 <= 2147483647, every entry of col in 0 .. n-1, every row index in 0 .. max(row0 + n) - 1, every
+ * selected gene in 0 .. G-1, T ng <= 2147483647 (gridDim.x).  That rowptr ascends from 0 to M, that no value is negative and that
+ * a max deg < 1 are the caller's to refuse (the kernel clamps what it reads). */
+int spadot_sepal_steps(const int *rowptr, const int *col, const long long *colptr, const int *ridx, const float *v, long long nnz,
+                       long long ridx_lo, long long ridx_hi, const long long *desc_host, const long long *desc_dev,
+                       const double *rate_host, const double *rate_dev, int T, int G, const int *genes, int ng, int gene_lo,
+                       int gene_hi, int init, int stop, long long steps, long long n_iter, double thresh, long long lds_limit,
+                       double *image, long long image_doubles, long long stride, double *H_prev, double *H0, int *iterations,
+                       int *done, double *trace, long long trace_len, void *stream);
 
 /* ---------------------------------------------------------------- trends stage (csrc/trends.hip)
  * The log-normalised counts of every time point, transposed, times a dense row-major fp64 W[n, C] (rows in the permuted order of

@@ -292,6 +292,8 @@ def model_lib():
         "spadot_cross_dense": [vp, vp, vp, vp, vp, ll, ll, ll, vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, ll, vp, vp, vp],
         "spadot_cross_sums": [vp, vp, ll, ci, vp, vp, ci, ci, ci, ll, ll, ll, vp, vp],
         "spadot_corr_sums": [vp, vp, vp, ll, ci, vp, vp, vp, vp, ci, ci, ci, ci, ll, ll, ll, ci, ci, vp, ll, vp, vp, vp, vp, vp, vp],
+        "spadot_sepal_steps": [vp, vp, vp, vp, vp, ll, ll, ll, vp, vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, ll, ll, cd, ll, vp, ll, ll,
+                               vp, vp, vp, vp, vp, ll, vp],
         "spadot_latent_knn": [vp, ci, ci, vp, vp, vp, vp, vp],
         "spadot_tsne_affinities": [vp, ci, vp, vp, vp, vp, vp, vp, vp],
         "spadot_tsne_steps": [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ll, ll, ci, ll, cd, ci, vp],

@@ -24,6 +24,8 @@
                                      [--n_perms 0] [--alpha 0.05] [--seed 0] [--device cuda:0]
     python -m spadot_amd embed   -i LATENT [--domains CSV] [-o DIR] [--prefix P] [--perplexity 30] [--n_iter 1000] [--early 250]
                                  [--learning_rate LR] [--per_timepoint] [--device cuda:0]
+    python -m spadot_amd sepal   -i COUNTS [-o DIR] [--prefix P] [--genes A,B | FILE] [--k 6] [--dt 0.1] [--thresh 1e-8]
+                                 [--n_iter 30000] [--device cuda:0]
 
 `preprocess` runs SPARK-X feature selection and the scaling on the device (spadot_amd.preprocess).  The balancing rule's gene
 clusters come from K-means by default; `--gene_clusters louvain` clusters SCTransform Pearson residuals with Louvain as the
@@ -68,7 +70,11 @@ semivariance of every selected gene over the pairs of spots in successive distan
 autocorrelation stops (spadot_amd.correlogram).  `embed` reads the latents and draws the map a user looks at first: a
 t-SNE of all time points together (or of every time point on its own with `--per_timepoint`) with sklearn's objective and
 optimiser and the repulsion summed exactly over all pairs in fp64, bitwise repeatable; with `--domains` the table and the plot
-carry the domain of every spot (spadot_amd.embed)."""
+carry the domain of every spot (spadot_amd.embed).  `sepal` reads the counts of `autocorr` and asks HOW LARGE the pattern
+of a gene is: the expression of every gene of `--genes` (default: all) diffuses over the k-nearest-neighbour graph of every time
+point, and the time until its entropy stops changing is the score of the gene -- a broad gradient takes long, fine-grained texture
+and noise are flat almost at once; a ranking by the scale of a pattern beside SPARK-X and Moran's I (spadot_amd.sepal, DESIGN
+7q)."""
 import argparse
 import os
 import sys
@@ -364,6 +370,25 @@ def build_parser():
                     help="One embedding per time point (one launch for all of them) instead of one joint embedding.")
     em.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
 
+    sp = sub.add_parser("sepal", help="How large the spatial pattern of a gene is: the time its expression takes to become "
+                                      "homogeneous when it diffuses over the spatial graph of every time point.")
+    sp.add_argument("-i", "--data", dest="data", type=str, required=True,
+                    help="The counts: the .npz written by preprocess (its raw counts of the selected genes), or raw counts as "
+                         "preprocess reads them (.npz or .h5ad).")
+    sp.add_argument("-o", "--output_dir", dest="output_dir", type=str,
+                    help="Output directory. Default: the same as where the data locates.")
+    sp.add_argument("--prefix", dest="prefix", type=str, default="", help="Prefix for the sepal tables. Default: ''")
+    sp.add_argument("--genes", dest="genes", type=str,
+                    help="The genes to score: a comma-separated list of names, or a file with one name per line. Default: all.")
+    sp.add_argument("--k", dest="k", type=int, default=6, help="Nearest neighbours per spot in the spatial graph. Default: 6")
+    sp.add_argument("--dt", dest="dt", type=float, default=0.1,
+                    help="Time step; dt n / (2 E) times the largest degree of the symmetric graph must stay below 1. Default: 0.1")
+    sp.add_argument("--thresh", dest="thresh", type=float, default=1e-8,
+                    help="A gene stops at the first step that changes its entropy by at most this. Default: 1e-8")
+    sp.add_argument("--n_iter", dest="n_iter", type=int, default=30000,
+                    help="Steps after which a gene that has not stopped is given up (it keeps the score dt * n_iter). Default: 30000")
+    sp.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
+
     lr = sub.add_parser("ligrec", help="Ligand-receptor tests between the spatial domains of every time point: the mean expression "
                                        "of every pair between every two domains, with a permutation null.")
     lr.add_argument("-i", "--data", dest="data", type=str, required=True,
@@ -503,6 +528,13 @@ def main(argv=None):
                 sys.exit(2)
         from .embed import embed
         embed(args)
+    elif args.cmd_choice == "sepal":
+        if not _exists(args.data):
+            print(f"SpaDOT sepal: the counts do not exist: {args.data}. Please make sure they are correctly specified.",
+                  file=sys.stderr)
+            sys.exit(2)
+        from .sepal import sepal_stage
+        sepal_stage(args)
     elif args.cmd_choice == "ligrec":
         for what, path in (("counts", args.data), ("domains table", args.domains), ("interactions table", args.interactions)):
             if not _exists(path):

@@ -1,5 +1,5 @@
 """The launches of the analysis stages (silhouette, gmm, neighbors, cooccurrence, autocorr, ligrec, hotspots, modules, ripley, correlogram,
-embed) in
+embed, sepal) in
 libspadot_model.so (include/spadot_model.h).  A *_check refuses, before any launch, what the library would refuse or cannot see (ranges that only a
 reduction on the device knows: one host round trip); a *_launch hands over what the check returned.  CPU tensors raise."""
 import ctypes
@@ -1372,3 +1372,190 @@ def tsne_steps_launch(desc, desc_dev, rowptr, col, val, state, it0, steps, early
                                        _p(s["att"]), _p(s["blk"]), _p(s["grad"]), _p(s["Z"]), _p(s["kl"]), int(s["kl"].shape[1]), it0,
                                        steps, early, float(exaggeration), int(bool(two)), _stream())
     launched(rc, "spadot_tsne_steps", EMBED_LIMITS)
+
+
+SEPAL_DESC = LOCAL_DESC            # the descriptor of moran.edge_csr; column 2 holds the entries of the symmetric CSR
+SEPAL_MAX = 2147483647             # spots, CSR entries and stored entries (int32), steps, and workgroups of a call (gridDim.x)
+SEPAL_THREADS = 1024               # the workgroup: the summation order of the entropy depends on it and on n alone
+SEPAL_SPT = 12                     # spots a thread holds in registers between the two barriers of a step
+SEPAL_LDS_FIXED = 512              # LDS beside the image: the reduction slots, the broadcast words, the segment bounds
+SEPAL_LDS_BYTES = SEPAL_LDS_FIXED + 8 * SEPAL_SPT * SEPAL_THREADS          # 98816: 12288 spots
+SEPAL_STEPS = 2048                 # steps per launch of sepal_steps
+SEPAL_LIMITS = ("1 <= steps and n_iter <= 2147483647, thresh >= 0 and finite, a rate > 0 and finite for every time point with edges, "
+                "1 <= n <= 2147483647 spots and at most 2147483647 CSR entries per time point, at most 2147483647 stored entries, "
+                "every entry of col in 0 .. n-1, every row index inside the time points, every selected gene inside the genes, at "
+                "most 2147483647 workgroups per call")
+
+
+def sepal_rate(dt, n, M):
+    """a = dt n / M in fp64, M = 2 E the entries of the symmetric CSR: the product rounded, then the quotient (0.0 where M = 0)."""
+    return float(dt) * int(n) / int(M) if int(M) > 0 else 0.0
+
+
+def sepal_max_dt(n, M, deg):
+    """The largest fp64 dt with sepal_rate(dt, n, M) * deg < 1 for a largest degree deg >= 1 (inf without edges)."""
+    n, M, deg = int(n), int(M), int(deg)
+    if M < 1 or deg < 1:
+        return float("inf")
+    y = M / (n * deg)
+    while sepal_rate(y, n, M) * deg >= 1.0:
+        y = float(np.nextafter(y, 0.0))
+    while sepal_rate(float(np.nextafter(y, np.inf)), n, M) * deg < 1.0:
+        y = float(np.nextafter(y, np.inf))
+    return y
+
+
+def sepal_lds_bytes(n):
+    """The LDS bytes a workgroup needs to keep the image of a time point of n spots."""
+    return SEPAL_LDS_FIXED + 8 * int(n)
+
+
+def sepal_stride(desc, lds_limit=None):
+    """The doubles of one item's row of the state's image, as the library computes it: the largest n, plus the largest n of
+    the time points whose image does not fit in LDS (the second slab of that path; 0 if all fit)."""
+    lds_limit = _lds_limit(lds_limit, SEPAL_LDS_BYTES)
+    return max(int(n) for n in desc[:, 1]) + max([int(n) for n in desc[:, 1] if sepal_lds_bytes(n) > lds_limit] or [0])
+
+
+def sepal_check(rowptr, col, colptr, ridx, values, genes, desc, dt, thresh, n_iter, steps):
+    """The refusals of sepal_steps, before any launch: dt, thresh, n_iter and steps, the limits from the descriptor, then per
+    time point the range of col, the order of rowptr and the largest degree, the range of the row indices and of the selected
+    genes, the order of colptr and the smallest value and whether all are finite by reductions on the device (one host round
+    trip); last dt against the largest degree: a max deg >= 1 is refused with the largest admissible dt.  Returns (the
+    descriptor with columns 6 and 7 filled in, the smallest row index, the largest, the smallest selected gene, the largest, the
+    rates fp64 [T]); ValueError otherwise."""
+    need_cuda(rowptr, col, colptr, ridx, values, genes)
+    desc = _host_desc(desc, SEPAL_DESC, "time point")
+    T = int(desc.shape[0])
+    dt, thresh, n_iter, steps = float(dt), float(thresh), int(n_iter), int(steps)
+    if not (dt > 0.0 and np.isfinite(dt)) or not (thresh >= 0.0 and np.isfinite(thresh)):
+        raise ValueError(f"sepal takes a finite dt > 0 and a finite thresh >= 0 (got dt = {dt}, thresh = {thresh})")
+    if not 1 <= n_iter <= SEPAL_MAX or not 1 <= steps <= SEPAL_MAX:
+        raise ValueError(f"sepal takes 1 to {SEPAL_MAX} steps in all and per launch (got n_iter = {n_iter}, steps = {steps})")
+    _typed((rowptr, torch.int32, "rowptr"), (col, torch.int32, "col"), (ridx, torch.int32, "ridx"), (colptr, torch.int64, "colptr"),
+           (values, torch.float32, "values"), (genes, torch.int32, "genes"))
+    (G, nnz), ng = _csc_sizes(colptr, ridx, values, SEPAL_MAX), int(genes.numel())
+    if ng < 1:
+        raise ValueError("spadot_sepal_steps takes at least one selected gene")
+    rows = 0
+    for t, (eoff, n, M, row0, _gid, roff, _lo, _hi) in enumerate(desc.tolist()):
+        _refuse_time_point(t, "spadot_sepal_steps", desc[t].tolist(), n, M, SEPAL_MAX,
+                           eoff >= 0 and roff >= 0 and 0 <= row0 <= SEPAL_MAX)
+        if eoff + M > col.numel() or roff + n + 1 > rowptr.numel():
+            raise ValueError(f"time point {t}: its rows or edges reach past the end of the tensors")
+        rows = max(rows, row0 + n)
+    if T * ng > SEPAL_MAX:
+        raise ValueError(f"the call holds more than {SEPAL_MAX} workgroups (the grid of one launch)")
+    zero = torch.zeros((), dtype=torch.int64, device=colptr.device)
+    degs = [torch.diff(rowptr[roff:roff + n + 1]).max().long() for _e, n, _M, _r, _g, roff, *_rest in desc.tolist()]
+    vals = [values.min() < 0, ~torch.isfinite(values).all()] if nnz > 0 else [zero, zero]
+    stats = (_csr_stats(rowptr, col, desc, zero) + _csc_stats(colptr, ridx, zero) + [s.long() for s in torch.aminmax(genes)]
+             + degs + [v.long() for v in vals])
+    stats = torch.stack(stats).cpu().numpy()                                # the one host round trip ahead of the launch
+    _refuse_csr(desc, stats[:5 * T].reshape(T, 5))
+    ridx_lo, ridx_hi, c0, c1, unordered, gene_lo, gene_hi = (int(v) for v in stats[5 * T:5 * T + 7])
+    _refuse_rows(ridx_lo, ridx_hi, nnz, rows)
+    _refuse_genes(gene_lo, gene_hi, G)
+    _refuse_colptr(c0, c1, unordered, nnz)
+    if stats[-1]:
+        raise ValueError("the values hold entries that are not finite: sepal diffuses finite values >= 0")
+    if stats[-2]:
+        raise ValueError("the values hold negative entries: sepal diffuses finite values >= 0")
+    rate = np.zeros(T, dtype=np.float64)
+    for t, deg in enumerate(stats[5 * T + 7:6 * T + 7].tolist()):
+        n, M = int(desc[t, 1]), int(desc[t, 2])
+        rate[t] = sepal_rate(dt, n, M)
+        if M > 0 and not rate[t] * deg < 1.0:
+            raise ValueError(f"dt = {dt} is too large for time point {t}: with {n} spots, {M // 2} edges and a largest degree of "
+                             f"{deg} the rate a = dt n / (2 E) = {rate[t]} gives a max deg >= 1 and the explicit step is "
+                             f"unstable; the largest admissible dt is {sepal_max_dt(n, M, deg)!r}")
+        if M > 0 and not rate[t] > 0.0:
+            raise ValueError(f"dt = {dt} gives time point {t} the rate {rate[t]}: it must be above 0")
+    return desc, ridx_lo, ridx_hi, gene_lo, gene_hi, rate
+
+
+def sepal_state(desc, ng, device, lds_limit=None, trace_len=0):
+    """The per-item state of sepal_launch for a descriptor, items = T ng: image fp64 [items, sepal_stride] (zeros), H_prev and H0
+    fp64 [items] (NaN), iterations and done int32 [items] (zeros) and, with trace_len, trace fp64 [items, trace_len] (NaN)."""
+    items = int(desc.shape[0]) * int(ng)
+    state = dict(image=torch.zeros((items, sepal_stride(desc, lds_limit)), dtype=torch.float64, device=device),
+                 H_prev=torch.full((items,), float("nan"), dtype=torch.float64, device=device),
+                 H0=torch.full((items,), float("nan"), dtype=torch.float64, device=device),
+                 iterations=torch.zeros(items, dtype=torch.int32, device=device),
+                 done=torch.zeros(items, dtype=torch.int32, device=device))
+    if trace_len:
+        state["trace"] = torch.full((items, int(trace_len)), float("nan"), dtype=torch.float64, device=device)
+    return state
+
+
+def _sepal_state_ok(state, items, stride):
+    for name, dt in (("image", torch.float64), ("H_prev", torch.float64), ("H0", torch.float64), ("iterations", torch.int32),
+                     ("done", torch.int32)):
+        t = state[name]
+        if t.dtype != dt or not t.is_contiguous() or int(t.shape[0]) != items or (name != "image" and t.numel() != items):
+            raise ValueError(f"the state's {name} must be a contiguous {dt} tensor of {items} items (got {tuple(t.shape)} {t.dtype})")
+    if state["image"].dim() != 2 or int(state["image"].shape[1]) < stride:
+        raise ValueError(f"the state's image must hold {stride} doubles per item (got {tuple(state['image'].shape)})")
+    trace = state.get("trace")
+    if trace is not None and (trace.dtype != torch.float64 or not trace.is_contiguous() or trace.dim() != 2
+                              or int(trace.shape[0]) != items or int(trace.shape[1]) < 1):
+        raise ValueError(f"the state's trace must be a contiguous float64 tensor [{items}, columns >= 1] (got {tuple(trace.shape)})")
+
+
+def sepal_launch(rowptr, col, colptr, ridx, values, genes, checked, state, init, steps, n_iter, thresh, stop=True, lds_limit=None,
+                 desc_dev=None, rate_dev=None):
+    """One launch of at most `steps` further steps of every item that is not done, on the state of sepal_state, for what
+    sepal_check has returned (the library checks the descriptor again, on the host).  init: the first launch, which builds the
+    images and H0; stop: apply the stop rule.  lds_limit must be the one the state was made for.  No host synchronisation."""
+    desc, ridx_lo, ridx_hi, gene_lo, gene_hi, rate = checked
+    need_cuda(rowptr, col, colptr, ridx, values, genes, desc_dev, rate_dev, *state.values())
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    rate = np.ascontiguousarray(rate, dtype=np.float64)
+    T, G, ng = int(desc.shape[0]), int(colptr.numel()) - 1, int(genes.numel())
+    lds_limit = _lds_limit(lds_limit, SEPAL_LDS_BYTES)
+    _sepal_state_ok(state, T * ng, sepal_stride(desc, lds_limit))
+    dev = colptr.device
+    if desc_dev is None:
+        desc_dev = torch.as_tensor(desc, device=dev)
+    if rate_dev is None:
+        rate_dev = torch.as_tensor(rate, device=dev)
+    image, trace = state["image"], state.get("trace")
+    rc = model_lib().spadot_sepal_steps(_p(rowptr), _p(col), _p(colptr), _p(ridx), _p(values), int(ridx.numel()), ridx_lo, ridx_hi,
+                                        _host(desc), _p(desc_dev), _host(rate), _p(rate_dev), T, G, _p(genes), ng, gene_lo, gene_hi,
+                                        int(bool(init)), int(bool(stop)), int(steps), int(n_iter), float(thresh), lds_limit,
+                                        _p(image), int(image.numel()), int(image.shape[1]), _p(state["H_prev"]), _p(state["H0"]),
+                                        _p(state["iterations"]), _p(state["done"]), _p(trace),
+                                        int(trace.shape[1]) if trace is not None else 0, _stream())
+    launched(rc, "spadot_sepal_steps", SEPAL_LIMITS)
+    return state
+
+
+def sepal_steps(rowptr, col, colptr, ridx, values, genes, desc, dt, thresh=1e-8, n_iter=30000, steps_per_launch=None, stop=True,
+                lds_limit=None, state=None, trace_len=0):
+    """The diffusion of every (time point, selected gene) until it stops or has taken n_iter steps (include/spadot_model.h:
+    spadot_sepal_steps).  rowptr, col int32: the symmetric CSR of the time points back to back; colptr int64, ridx int32 and
+    values fp32: the CSC arrays of a DeviceCounts; genes int32: the selected genes; desc: int64 [T, 8] on the host as
+    moran.edge_csr lays it out (columns 6 and 7, the range of col, are filled in here); dt: the time step, from which the rate
+    of a time point is sepal_rate(dt, n, M).  Launches of steps_per_launch (default 2048) steps follow one another until every item is
+    done or has reached n_iter; between two launches the host reads the flags and the counts, one small copy.  stop=False: no
+    stop rule, exactly n_iter steps.  lds_limit: the LDS bytes a workgroup may use (default and at most 98816); a time point
+    whose image does not fit keeps it in the state, with the same bits.  state: a sepal_state to run in (default: a fresh one;
+    trace_len: with a trace of that many columns).  Returns the state.  ValueError, before any launch, outside the limits;
+    RuntimeError for a CPU tensor."""
+    steps = SEPAL_STEPS if steps_per_launch is None else int(steps_per_launch)
+    checked = sepal_check(rowptr, col, colptr, ridx, values, genes, desc, dt, thresh, n_iter, steps)
+    dev, ng = colptr.device, int(genes.numel())
+    if state is None:
+        state = sepal_state(checked[0], ng, dev, lds_limit, trace_len)
+    else:
+        need_cuda(*state.values())
+        _sepal_state_ok(state, int(checked[0].shape[0]) * ng, sepal_stride(checked[0], _lds_limit(lds_limit, SEPAL_LDS_BYTES)))
+    desc_dev, rate_dev = torch.as_tensor(checked[0], device=dev), torch.as_tensor(checked[5], device=dev)
+    init = True
+    while True:
+        sepal_launch(rowptr, col, colptr, ridx, values, genes, checked, state, init, steps, n_iter, thresh, stop, lds_limit, desc_dev,
+                     rate_dev)
+        init = False
+        flags = torch.stack([state["done"], state["iterations"]]).cpu().numpy()      # the one small copy between two launches
+        if np.all((flags[0] != 0) | (flags[1] >= int(n_iter))):
+            return state
