@@ -236,7 +236,7 @@ int spadot_cluster_losses_backward(const float *z, const float *centres, const f
                                    float *dz, void *stream);
 /* forward AND dz = d(g_km[0] * km + g_ot[0] * ot) / dz in ONE launch, for gradient seeds known when the forward runs (the loss
  * weights of _train_utils.py:205-212, device scalars).  Same arithmetic as forward + backward.  Returns -95 when the shape
- * does not take the kernel's one-chunk fast path (K <= 16, b * D <= 10240): call forward / backward then. */
+ * does not take the kernel's one-chunk fast path (K <= 16, K * D <= 512, b * D <= 10240): call forward / backward then. */
 int spadot_cluster_losses_fb(const float *z, const long long *labels_all, const long long *seed_ids, const float *centres,
                              const float *prev_centres, const float *gamma, const long long *cluster_list, int b, int D, int K,
                              int Kp, int Kl, int do_km, int do_ot, const float *g_km, const float *g_ot, float *out2,

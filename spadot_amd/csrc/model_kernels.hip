@@ -1993,7 +1993,7 @@ constexpr int CL_MAXK = 64, CL_MAXD = 64, CL_KREG = 16;
 constexpr int CL_MAX_DYN_LDS = 108 * 1024;        // 160 KiB less the kernel's static arrays (centres, previous centres, plan: 48.6 KiB)
 // FB: the same launch also writes dz = d(g_km km + g_ot ot) / dz for gradient seeds that are known when the forward runs (the
 // loss weights, device scalars): k_cluster_losses_bwd's arithmetic on the state this kernel has in LDS anyway.  Host-side
-// conditions (spadot_cluster_losses_fb): the fast path (K <= CL_KREG), the whole batch in ONE chunk, and room for
+// conditions (spadot_cluster_losses_fb): the fast path (K <= CL_KREG, K * D <= 512), the whole batch in ONE chunk, and room for
 // [centres | d means | distances] in the segment-partial buffer.
 template <bool FB>
 __global__ __launch_bounds__(512) void k_cluster_losses_fwd(const float *__restrict__ z, const long long *__restrict__ labels_all,
@@ -2085,9 +2085,10 @@ __global__ __launch_bounds__(512) void k_cluster_losses_fwd(const float *__restr
             }
         }
         __syncthreads();
-        if (K <= CL_KREG && D <= (int)blockDim.x) {
+        if (K <= CL_KREG && K * D <= (int)blockDim.x) {
             // fast path: thread = (row segment, column) keeps the K partial sums of its segment in registers;
-            // the segments are then added in order (fixed order => reproducible), far fewer serial LDS reads
+            // the segments are then added in order (fixed order => reproducible), far fewer serial LDS reads.
+            // The fold below fills PAIRS slot 0 only, so every (cluster, column) pair has to sit there: K * D <= 512.
             const int segs = (int)blockDim.x / D, seg = t / D, d = t - seg * D;
             const int per = (rows + segs - 1) / segs;
             float av[CL_KREG];
@@ -2703,7 +2704,7 @@ int spadot_cluster_losses_forward(const float *z, const long long *labels_all, c
     if (chunk < CL_MAXK) chunk = CL_MAXK;
     chunk = (chunk + 7) / 8 * 8;
     size_t lds = sizeof(float) * (size_t)chunk * D + sizeof(int) * (size_t)chunk;
-    if (K <= CL_KREG && D <= 512) lds += sizeof(float) * (size_t)(512 / D) * K * (D + 1);
+    if (K <= CL_KREG && K * D <= 512) lds += sizeof(float) * (size_t)(512 / D) * K * (D + 1);
     if (lds > (size_t)CL_MAX_DYN_LDS) return -22;
     static PerDeviceFlag attr_set;     
     if (!attr_set) { (void)hipFuncSetAttribute((const void *)k_cluster_losses_fwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, CL_MAX_DYN_LDS); attr_set = true; }
@@ -2725,7 +2726,7 @@ int spadot_cluster_losses_fb(const float *z, const long long *labels_all, const 
     if (chunk < CL_MAXK) chunk = CL_MAXK;
     chunk = (chunk + 7) / 8 * 8;
     const size_t part = (size_t)(512 / D) * K * (D + 1);
-    if (K > CL_KREG || chunk < b || part < 2 * (size_t)K * D + (do_ot ? (size_t)Kp * Kl : 0)) return -95;
+    if (K > CL_KREG || K * D > 512 || chunk < b || part < 2 * (size_t)K * D + (do_ot ? (size_t)Kp * Kl : 0)) return -95;
     const size_t lds = sizeof(float) * (size_t)chunk * D + sizeof(int) * (size_t)chunk + sizeof(float) * part;
     if (lds > (size_t)CL_MAX_DYN_LDS) return -95;
     static PerDeviceFlag attr_set;     

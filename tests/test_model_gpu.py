@@ -11,6 +11,7 @@ import torch
 
 from conftest import load_golden
 from oracle import model_oracle as mo
+from step_tail_cases import head_inputs, latent_head_ref
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -664,28 +665,19 @@ def test_ln_act_matches_layernorm_leakyrelu(ops, b, F_):
 def test_latent_head_vs_torch_formulas(ops, b, Ls, Lg):
     """ops.latent_head against the line-by-line torch formulation of SpaDOT.py:78-93 in fp64 (values and
     gradients w.r.t. the GAT_fc output and the SVGP posterior)."""
-    rng = np.random.default_rng(b)
-    zg = T(rng.normal(size=(b, 2 * Lg)) * 0.7); p_m = T(rng.normal(size=(b, Ls))); p_v = T(rng.uniform(0.05, 2.0, size=(b, Ls)))
-    eps = T(rng.normal(size=(b, Ls + Lg))).float().double()            # the op takes fp32 noise
-    gl = T(rng.normal(size=(b, Ls + Lg))); wk, wa = 0.37, -1.3
-    # reference
-    zr, pmr, pvr = (t.clone().requires_grad_(True) for t in (zg, p_m, p_v))
-    mu, var = zr[:, :Lg], torch.exp(zr[:, Lg:])
-    s_lat = pmr + eps[:, :Ls] * torch.sqrt(pvr)
-    g_lat = mu + eps[:, Ls:] * torch.sqrt(var)
-    kl = -0.5 * torch.sum(1 + torch.log(var) - mu.pow(2) - var) / Lg
-    al = torch.nn.functional.mse_loss(s_lat.norm(dim=1) / Ls, g_lat.norm(dim=1) / Lg, reduction="sum")
-    lat_r = torch.cat([s_lat, g_lat], 1)
-    ((lat_r * gl).sum() + wk * kl + wa * al).backward()
+    zg, p_m, p_v, eps, gl = head_inputs(b, Ls, Lg)
+    wk, wa = 0.37, -1.3
+    # reference (the fp64 formulas, shared with the edge cases of test_step_tail_edges_gpu.py)
+    want = latent_head_ref(zg, p_m, p_v, eps, gl, Ls, Lg, wk, wa)
     # device
     zd = zg.to(DEV, torch.float32).requires_grad_(True)
     pmd, pvd = (t.to(DEV).requires_grad_(True) for t in (p_m, p_v))
     lat, kl_d, al_d = ops.latent_head(zd, pmd, pvd, eps.to(DEV, torch.float32), Ls, Lg)
     ((lat * gl.to(DEV, torch.float32)).sum() + wk * kl_d + wa * al_d).backward()
-    np.testing.assert_allclose(lat.detach().cpu().numpy(), lat_r.detach().numpy(), rtol=2e-6, atol=2e-6)
-    assert float(kl_d) == pytest.approx(float(kl), rel=1e-5) and float(al_d) == pytest.approx(float(al), rel=1e-5)
-    for name, d, r in (("zg", zd, zr), ("p_m", pmd, pmr), ("p_v", pvd, pvr)):
-        ref = r.grad.numpy()
+    np.testing.assert_allclose(lat.detach().cpu().numpy(), want["latent"].numpy(), rtol=2e-6, atol=2e-6)
+    assert float(kl_d) == pytest.approx(want["kl"], rel=1e-5) and float(al_d) == pytest.approx(want["al"], rel=1e-5)
+    for name, d in (("zg", zd), ("p_m", pmd), ("p_v", pvd)):
+        ref = want[name].numpy()
         np.testing.assert_allclose(d.grad.cpu().numpy(), ref, rtol=1e-4, atol=1e-5 * np.abs(ref).max(), err_msg=name)
 
 
@@ -707,7 +699,7 @@ def test_latent_head_draws_its_own_standard_normals(ops):
     assert torch.equal(lat3, lat1)
 
 
-@pytest.mark.parametrize("b,K,absent", [(512, 10, False), (64, 10, True), (700, 7, True)])
+@pytest.mark.parametrize("b,K,absent", [(512, 10, False), (64, 10, True), (700, 7, True), (700, 7, False)])
 def test_cluster_losses_vs_oracle_and_torch_gradient(ops, b, K, absent):
     """ops.cluster_losses: values against the oracle's restatement of _train_utils.py:240-253/272-307, the
     gradient against torch autograd of the same formulas in fp64."""
