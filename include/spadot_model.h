@@ -193,7 +193,7 @@ int spadot_svgp_grad_tail(const double *q1, const double *q2, const double *Kdt,
                           void *stream);
 /* z [b, 2L] fp32 = SVGP_fc output (mu | logvar) -> mu, var = exp(logvar), w = 1/var, mu w, each [b, L] fp64
  * (encoder.py:31-34 + the first element-wise steps of svgp.py:62-70).  grad_tail's dz [b, 2L] fp32 is the matching
- * gradient (d/dlogvar = d/dvar * var); dmu/dvar may then be NULL. */
+ * gradient (d/dlogvar = d/dvar * var); dmu/dvar may then both be NULL (one of the pair alone is refused: -22). */
 int spadot_svgp_pre(const float *z, int b, int L, double *mu, double *var, double *w, double *muw, void *stream);
 /* ... and A[l, i, :] = K_nm[i, :] / var[i, l]  ([L, b, m] fp64) in the same launch */
 int spadot_svgp_pre2(const float *z, const double *Kn, int b, int L, int m, double *mu, double *var, double *w, double *muw,
@@ -280,7 +280,8 @@ int spadot_sgemm_small(int mode, const float *A, int lda, const float *B, int ld
  * next launch: spadot_enc_bn_map (statistics of 16 columns of h1, y1, running statistics, part), spadot_enc_bn_fc (h2 = sum of
  * part -- stored without the map's bias, which BatchNorm's lin_bias carries --, y2, running statistics, pz), and either
  * spadot_enc_sum_z (z = bias + sum of pz) or spadot_svgp_pre2_partials (spadot_svgp_pre2 reading z from pz; it also stores z).
- * b <= 512, F1 % 16 == 0, F2 % 4 == 0, F2 <= 128, Q <= 32.  y1 is bit for bit what spadot_bn_act_forward writes. */
+ * b <= 512, F1 % 16 == 0, F2 % 4 == 0, F2 <= 128, Q <= 32; both readers of pz take 1 .. 64 partials.  y1 is bit for bit what
+ * spadot_bn_act_forward writes. */
 int spadot_enc_fused_supported(int b, int F1, int F2, int Q);
 long long spadot_enc_fused_workspace(int b, int F1, int F2, int Q);
 int spadot_enc_bn_map(const float *h1, const float *lin_bias, const float *gamma, const float *beta, float *running_mean,

@@ -306,7 +306,7 @@ int spadot_enc_bn_fc(const float *part, int nparts, const float *lin_bias, const
 }
 
 int spadot_enc_sum_z(const float *pz, int nparts, const float *bias, int b, int Q, float *z, void *stream) {
-    if (!pz || !bias || !z || nparts < 1 || b <= 0 || Q <= 0) return -22;
+    if (!pz || !bias || !z || nparts < 1 || nparts > 64 || b <= 0 || Q <= 0) return -22;      // (64: what spadot_svgp_pre2_partials takes)
     hipLaunchKernelGGL(k_enc_sum_z, dim3((b * Q + 255) / 256), dim3(256), 0, (hipStream_t)stream, pz, nparts, bias, b, Q, z);
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }

@@ -566,7 +566,7 @@ __global__ __launch_bounds__(256) void k_kernel_matrix(const T *__restrict__ x, 
 // (svgp.py:50,75,87-88): 2 launches instead of ~700 library kernels per training step.
 // ------------------------------------------------------------------------------------------
 // 512 threads (2 waves per SIMD, 256 VGPRs), tile grid T <= 31.  A TS x TS tile keeps its RS x RS core
-// (RS = min(TS, 7)) in registers and the L-shaped rest in a thread-private LDS strip (slot-major, so the 64
+// (RS = min(TS, SWEEP_RS)) in registers and the L-shaped rest in a thread-private LDS strip (slot-major, so the 64
 // lanes of a wave touch 64 consecutive doubles: conflict-free): TS = 8, 9 reach m = 248, 279 without the
 // compiler spilling the tile (a spilled build measured ~10x slower; a 256-thread / 512-register build 4-40x).
 constexpr int SWEEP_NT = 512;
@@ -2660,7 +2660,7 @@ int spadot_svgp_grad_tail(const double *q1, const double *q2, const double *Kdt,
                           const double *p_m, const double *mu, const double *w, const double *g_kl, const double *g_mu,
                           const double *g_var, int b, int L, double c, double *dmu, double *dvar, float *dz,
                           void *stream) {
-    if (b <= 0 || L <= 0 || (!dz && !(dmu && dvar))) return -22;
+    if (b <= 0 || L <= 0 || (!dz && !dmu) || (!dmu != !dvar)) return -22;      // (dmu and dvar go together: the kernel writes both)
     hipLaunchKernelGGL(k_svgp_grad_tail, dim3((b * L + 255) / 256), dim3(256), 0, (hipStream_t)stream, q1, q2, Kdt, p_v,
                        ktilde, p_m, mu, w, g_kl, g_mu, g_var, b, L, c, dmu, dvar, dz);
     return hipGetLastError() == hipSuccess ? 0 : -5;

@@ -270,8 +270,9 @@ def test_reduction_kernels_gradients_vs_torch(ops):
 @pytest.mark.parametrize("L,m", [(1, 1), (3, 17), (3, 95), (3, 96), (4, 100), (3, 128), (10, 204), (10, 217), (10, 236), (4, 248), (40, 256), (3, 257), (40, 261),
                                  (5, 272), (3, 273), (3, 279), (3, 288), (2, 289), (3, 310), (2, 311), (2, 389), (10, 600), (2, 621), (2, 870), (1, 1300)])
 def test_spd_inverse_logdet_vs_torch(ops, L, m):
-    """Batched SPD inverse + logdet (sweep kernel: register tiles up to 279, + LDS border up to 310; recursive two-block elimination beyond) against
-    torch.linalg on matrices conditioned like the SVGP's Sigma_l (jitter 1e-2, cond ~1e6)."""
+    """Batched SPD inverse + logdet (sweep kernel: register tiles up to 279; recursive two-block elimination beyond -- ops splits
+    at 279, so the kernel's widest tiles, m = 280 .. 310 with their border in LDS, are reached by test_svgp_edges_gpu.py's direct
+    calls only) against torch.linalg on matrices conditioned like the SVGP's Sigma_l (jitter 1e-2, cond ~1e6)."""
     rng = np.random.default_rng(m)
     B = rng.normal(size=(L, m, max(2, m // 3)))
     A = T(B @ B.transpose(0, 2, 1) * 50.0 + 1e-2 * np.eye(m)).to(DEV).requires_grad_(True)
