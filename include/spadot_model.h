@@ -21,6 +21,7 @@
  *   spadot_gmm_*       no counterpart in the reference: sklearn.mixture.GaussianMixture(covariance_type="full") per (data set, K)
  *   spadot_weighted_moments  no counterpart in the reference: X_csc.T @ W of the log-normalised counts, three moments
  *   spadot_nhood_counts      no counterpart in the reference: the label-pair edge counts of squidpy's gr.nhood_enrichment
+ *   spadot_territory_counts  no counterpart in the reference: the connected pieces of every domain (scipy's csgraph.connected_components)
  *   spadot_cooccur_counts    no counterpart in the reference: the label-pair counts by distance of squidpy's gr.co_occurrence
  *   spadot_cooccur_null      no counterpart in the reference: the same counts under relabelings (a random-labelling null)
  *   spadot_ripley_*          no counterpart in the reference: the pair, nearest-neighbour and empty-space counts of squidpy's gr.ripley
@@ -745,6 +746,28 @@ int spadot_gmm_estep(const double *x, int d, int P, const long long *prob, int K
  * g <= 2147483647.  A label >= K is the caller's to refuse (its edges are not counted). */
 int spadot_nhood_counts(const int *src, const int *dst, const unsigned char *labels, const long long *desc_host,
                         const long long *desc_dev, int G, int K_max, long long lds_limit, int *out, void *stream);
+
+/* ---------------------------------------------------------------- territories (csrc/territories.hip)
+ * The connected pieces of every domain of many (graph, labeling) problems in ONE launch, one workgroup per (problem,
+ * labeling).  A territory is a connected component of the subgraph that keeps only the edges whose two ends carry the same
+ * label (direction ignored; duplicates, two-way edges and self loops change nothing); its id is the smallest node it contains.
+ * Integers only: integer min / add / max atomics inside one workgroup, none across workgroups (a problem gives the same
+ * integers alone, in any batch, on either path, run after run; tests/territories_ref.py).
+ * src, dst, labels and the columns 0 .. 11 of desc [G, 14] int64 (once on the host, checked here; once on the device) are those
+ * of spadot_nhood_counts, the permuted labelings included.  Further columns:
+ *   12 first node of the problem in ids / sizes (-1: not asked for; otherwise the n ids and sizes of its FIRST labeling are written)
+ *   13 first int of the problem's slabs in scratch (checked: the sum of the slabs of the problems before; ignored on the LDS path)
+ * out: int64 [sum L, K_max, 4] per label value (count of territories, size of the largest, territories of one node, sum of
+ * size^2), zeros for a label value without nodes or >= K; written completely.  ids, sizes: int32 [n_ids] (may be null when no
+ * problem asks).  status: int32 [sum L, 2] = (0, or 1 when the round cap n + 1 was reached: the other outputs of that item are
+ * then meaningless; rounds run).
+ * A problem keeps its parents, sizes and labels in LDS where 1024 + 8 n + (n rounded up to 16) <= lds_limit (at most 163840;
+ * larger values mean 163840: n <= 18 090) and otherwise in a slab of 2 n + ceil(n / 4) ints per labeling of `scratch` (int32
+ * [n_scratch]; may be null when every problem fits); the work stays inside the workgroup's own slab.
+ * Return -22 for null or inconsistent arguments and -7, before any launch, outside the limits of spadot_nhood_counts. */
+int spadot_territory_counts(const int *src, const int *dst, const unsigned char *labels, const long long *desc_host,
+                            const long long *desc_dev, int G, int K_max, long long lds_limit, long long *out, int *ids,
+                            int *sizes, long long n_ids, int *status, int *scratch, long long n_scratch, void *stream);
 
 /* ---------------------------------------------------------------- co-occurrence by distance (csrc/cooccur.hip)
  * N[a, b, t] = #{ordered pairs (i, j), i != j : lab[i] = a, lab[j] = b, d2(i, j) <= r2[t]} of P (spot set, labeling,

@@ -26,6 +26,8 @@
                                  [--learning_rate LR] [--per_timepoint] [--device cuda:0]
     python -m spadot_amd sepal   -i COUNTS [-o DIR] [--prefix P] [--genes A,B | FILE] [--k 6] [--dt 0.1] [--thresh 1e-8]
                                  [--n_iter 30000] [--device cuda:0]
+    python -m spadot_amd territories --domains CSV [-o DIR] [--prefix P] [--k 6] [--n_perms 1000] [--seed 0] [--min_size 0]
+                                     [--alpha 0.05] [--device cuda:0]
 
 `preprocess` runs SPARK-X feature selection and the scaling on the device (spadot_amd.preprocess).  The balancing rule's gene
 clusters come from K-means by default; `--gene_clusters louvain` clusters SCTransform Pearson residuals with Louvain as the
@@ -74,7 +76,11 @@ carry the domain of every spot (spadot_amd.embed).  `sepal` reads the
 of a gene is: the expression of every gene of `--genes` (default: all) diffuses over the k-nearest-neighbour graph of every time
 point, and the time until its entropy stops changing is the score of the gene -- a broad gradient takes long, fine-grained texture
 and noise are flat almost at once; a ranking by the scale of a pattern beside SPARK-X and Moran's I (spadot_amd.sepal, DESIGN
-7q)."""
+7q).  `territories` reads the domains table and looks at the map itself: the connected pieces of every domain on the
+k-nearest-neighbour graph of every time point (how many, the largest, the stray single spots, a contiguity between 0 and 1),
+each against `--n_perms` random relabelings, the territory of every spot and whether it lies on a border; with `--min_size S`
+every piece of fewer than S spots is handed to the domain it touches most and the cleaned map is written as
+refined_domains.csv, which every `--domains` stage reads (spadot_amd.territories)."""
 import argparse
 import os
 import sys
@@ -195,6 +201,26 @@ def build_parser():
                     help="Random relabelings (domain sizes kept) behind the z-scores and p-values. Default: 1000")
     nb.add_argument("--seed", dest="seed", type=int, default=0, help="Seed of the relabelings. Default: 0")
     nb.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
+
+    te = sub.add_parser("territories", help="The connected pieces of every spatial domain on the k-nearest-neighbour graph of "
+                                            "every time point: one piece or forty, which spots are strays, and a map "
+                                            "cleaned of them.")
+    te.add_argument("--domains", dest="domains", type=str, required=True,
+                    help="The domains.csv written by analyze: row, timepoint, kmeans, pixel_x, pixel_y.")
+    te.add_argument("-o", "--output_dir", dest="output_dir", type=str,
+                    help="Output directory. Default: the same as where the domains table locates.")
+    te.add_argument("--prefix", dest="prefix", type=str, default="", help="Prefix for the territory tables. Default: ''")
+    te.add_argument("--k", dest="k", type=int, default=6, help="Spatial neighbours per spot. Default: 6")
+    te.add_argument("--n_perms", dest="n_perms", type=int, default=1000,
+                    help="Random relabelings (domain sizes kept) behind the z-scores and p-values, 0 to 9999; 0: no test. "
+                         "Default: 1000")
+    te.add_argument("--seed", dest="seed", type=int, default=0, help="Seed of the relabelings. Default: 0")
+    te.add_argument("--min_size", dest="min_size", type=int, default=0,
+                    help="Hand every territory of fewer spots to the domain it touches most and write refined_domains.csv; 0: "
+                         "off, otherwise at least 2. Default: 0")
+    te.add_argument("--alpha", dest="alpha", type=float, default=0.05,
+                    help="Level of the adjusted p-value below which a domain is called contiguous or fragmented. Default: 0.05")
+    te.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
 
     co = sub.add_parser("cooccurrence", help="Co-occurrence of the spatial domains by distance: for every pair of domains, how "
                                              "many pairs of spots lie within each radius and the ratio to what the "
@@ -475,6 +501,13 @@ def main(argv=None):
             sys.exit(2)
         from .neighbors import neighbors
         neighbors(args)
+    elif args.cmd_choice == "territories":
+        if not _exists(args.domains):
+            print(f"SpaDOT territories: the domains table does not exist: {args.domains}. Please make sure it is correctly "
+                  "specified.", file=sys.stderr)
+            sys.exit(2)
+        from .territories import territories_stage
+        territories_stage(args)
     elif args.cmd_choice == "cooccurrence":
         if not _exists(args.domains):
             print(f"SpaDOT cooccurrence: the domains table does not exist: {args.domains}. Please make sure it is correctly "

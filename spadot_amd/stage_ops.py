@@ -1,5 +1,5 @@
-"""The launches of the analysis stages (silhouette, gmm, neighbors, cooccurrence, autocorr, ligrec, hotspots, modules, ripley, correlogram,
-embed, sepal) in
+"""The launches of the analysis stages (silhouette, gmm, neighbors, territories, cooccurrence, autocorr, ligrec, hotspots, modules, ripley,
+correlogram, embed, sepal) in
 libspadot_model.so (include/spadot_model.h).  A *_check refuses, before any launch, what the library would refuse or cannot see (ranges that only a
 reduction on the device knows: one host round trip); a *_launch hands over what the check returned.  CPU tensors raise."""
 import ctypes
@@ -257,6 +257,76 @@ def nhood_counts(src, dst, labels, desc, K_max, lds_limit=None, out=None):
     (default and at most 163840); a graph whose labels do not fit reads them from global memory.  Returns int32
     [sum L, K_max, K_max] (out: the tensor to write into).  ValueError, before any launch, outside the limits."""
     return nhood_launch(src, dst, labels, nhood_check(src, dst, labels, desc, K_max), K_max, lds_limit, out)
+
+
+TERRITORY_DESC = 14
+TERRITORY_LDS_BYTES = 163840
+TERRITORY_FIXED = 1024            # the per-label tables and flags of a workgroup, ahead of its per-node arrays
+TERRITORY_LIMITS = (NHOOD_LIMITS + "; a problem stays in LDS where 1024 + 8 n + (n rounded up to 16) <= lds_limit <= 163840 bytes (9 "
+                    "bytes a node: n <= 18090) and works in its scratch slab of 2 n + ceil(n / 4) ints per labeling otherwise")
+
+
+def territory_lds_bytes(n):
+    """The LDS bytes a problem of n nodes needs to stay on chip: the fixed tables, then parent, size (int32) and label byte."""
+    return TERRITORY_FIXED + 8 * n + ((n + 15) & ~15)
+
+
+def territory_slab_ints(n):
+    return 2 * n + (n + 3) // 4
+
+
+def territory_check(src, dst, labels, desc, K_max):
+    """The refusals of territory_counts, before any launch: those of nhood_check on the columns 0 .. 11 (limits, then the range
+    of the edge ends and the largest label by reductions on the device, one host round trip) and column 12 >= -1.  Returns the
+    descriptor with columns 10 and 11 filled in; ValueError otherwise."""
+    desc = _host_desc(desc, TERRITORY_DESC, "problem")
+    if (desc[:, 12] < -1).any():
+        raise ValueError(f"problem {int(np.flatnonzero(desc[:, 12] < -1)[0])}: inconsistent descriptor (column 12 is -1 or the first "
+                         f"node in ids)")
+    try:
+        desc[:, :NHOOD_DESC] = nhood_check(src, dst, labels, desc[:, :NHOOD_DESC], K_max)
+    except ValueError as e:
+        raise ValueError(str(e).replace("spadot_nhood_counts", "spadot_territory_counts")) from None
+    return desc
+
+
+def territory_launch(src, dst, labels, desc, K_max, lds_limit=None):
+    """The launch of territory_counts for a descriptor that territory_check has returned (the library checks it again, on the
+    host).  Column 13, the slab offsets, is filled in here, the scratch tensor made and the descriptor uploaded.  Returns (out int64 [items, K_max, 4], ids
+    int32, sizes int32 -- both of the length the descriptor's column 12 asks for --, status int32 [items, 2])."""
+    need_cuda(src, dst, labels)
+    desc = np.array(desc, dtype=np.int64, order="C", copy=True)
+    K_max, items = int(K_max), int(desc[:, 5].sum())
+    lds_limit = _lds_limit(lds_limit, TERRITORY_LDS_BYTES)
+    slabs = n_ids = 0
+    for g in range(desc.shape[0]):
+        n, L = int(desc[g, 1]), int(desc[g, 5])
+        if desc[g, 12] >= 0:
+            n_ids = max(n_ids, int(desc[g, 12]) + n)
+        if territory_lds_bytes(n) > lds_limit:
+            desc[g, 13] = slabs
+            slabs += L * territory_slab_ints(n)
+    dev = labels.device
+    out = torch.empty((items, K_max, 4), dtype=torch.int64, device=dev)
+    status = torch.empty((items, 2), dtype=torch.int32, device=dev)
+    ids = torch.empty(n_ids, dtype=torch.int32, device=dev)
+    sizes = torch.empty(n_ids, dtype=torch.int32, device=dev)
+    scratch = torch.empty(slabs, dtype=torch.int32, device=dev)
+    desc_dev = torch.as_tensor(desc, device=dev)
+    launched(model_lib().spadot_territory_counts(_p(src), _p(dst), _p(labels), _host(desc), _p(desc_dev), int(desc.shape[0]), K_max,
+                                                 lds_limit, _p(out), _p(ids) if n_ids else None, _p(sizes) if n_ids else None,
+                                                 n_ids, _p(status), _p(scratch) if slabs else None, slabs, _stream()),
+             "spadot_territory_counts", TERRITORY_LIMITS)
+    return out, ids, sizes, status
+
+
+def territory_counts(src, dst, labels, desc, K_max, lds_limit=None):
+    """The territories of many (graph, labeling) problems in ONE launch (include/spadot_model.h: spadot_territory_counts).  src,
+    dst int32 and labels uint8 device tensors, the graphs back to back; desc: int64 [G, 14] on the host as the header lays it
+    out (columns 10, 11 and 13 are filled in here).  lds_limit: the LDS bytes a workgroup may use (default and at most 163840); a
+    problem that needs more works in a slab of global scratch.  Returns (out, ids, sizes, status) as territory_launch does.
+    ValueError, before any launch, outside the limits."""
+    return territory_launch(src, dst, labels, territory_check(src, dst, labels, desc, K_max), K_max, lds_limit)
 
 
 COOCCUR_MAX_K = 32

@@ -184,6 +184,27 @@ def plot_domains(path, pixel_x, pixel_y, labels, timepoint):
     fig.savefig(path)
 
 
+def plot_territories(path, pixel_x, pixel_y, labels, small, timepoint, min_size):
+    """{prefix}{tp}_territories.png: the spots coloured by domain as plot_domains draws them, the spots of territories of fewer
+    than min_size spots ringed in black."""
+    import matplotlib
+    fig = _figure((5, 5))
+    ax = fig.add_subplot(1, 1, 1)
+    cmap = matplotlib.colormaps["tab10"]
+    x, y, labels, small = np.asarray(pixel_x), np.asarray(pixel_y), np.asarray(labels), np.asarray(small, dtype=bool)
+    for i, c in enumerate(np.unique(labels).tolist()):
+        m = labels == c
+        ax.scatter(x[m], y[m], s=10, color=cmap(i % 10), label=str(c), linewidths=0)
+    ax.scatter(x[small], y[small], s=24, facecolors="none", edgecolors="black", linewidths=0.6,
+               label=f"< {int(min_size)} spots")
+    ax.set_xlabel("pixel_x")
+    ax.set_ylabel("pixel_y")
+    ax.legend(title="kmeans", bbox_to_anchor=(1.05, 1), loc=2, borderaxespad=0.)
+    ax.set_title("Territories, time point: {}".format(timepoint))
+    fig.tight_layout()
+    fig.savefig(path)
+
+
 def plot_nhood(path, zscore, timepoint):
     """{prefix}{tp}_nhood.png: the neighbourhood-enrichment z-scores of one time point as a heat map (domain by neighbor), on
     a diverging scale centred at 0; a cell without a z-score (no variance under permutation) stays blank."""
