@@ -22,6 +22,7 @@
  *   spadot_weighted_moments  no counterpart in the reference: X_csc.T @ W of the log-normalised counts, three moments
  *   spadot_nhood_counts      no counterpart in the reference: the label-pair edge counts of squidpy's gr.nhood_enrichment
  *   spadot_territory_counts  no counterpart in the reference: the connected pieces of every domain (scipy's csgraph.connected_components)
+ *   spadot_hop_sums          no counterpart in the reference: hop distances from every domain and every spot (squidpy's gr.centrality_scores)
  *   spadot_cooccur_counts    no counterpart in the reference: the label-pair counts by distance of squidpy's gr.co_occurrence
  *   spadot_cooccur_null      no counterpart in the reference: the same counts under relabelings (a random-labelling null)
  *   spadot_ripley_*          no counterpart in the reference: the pair, nearest-neighbour and empty-space counts of squidpy's gr.ripley
@@ -768,6 +769,33 @@ int spadot_nhood_counts(const int *src, const int *dst, const unsigned char *lab
 int spadot_territory_counts(const int *src, const int *dst, const unsigned char *labels, const long long *desc_host,
                             const long long *desc_dev, int G, int K_max, long long lds_limit, long long *out, int *ids,
                             int *sizes, long long n_ids, int *status, int *scratch, long long n_scratch, void *stream);
+
+/* ---------------------------------------------------------------- hop distances (csrc/hops.hip)
+ * Level-synchronous breadth-first search from up to 32 source sets at once (one bit of a 32-bit mask per set) of many
+ * (graph, labeling) problems in ONE launch, one workgroup per item.  Direction is ignored; duplicates, two-way edges and self
+ * loops change nothing.  Integers only: integer or / add atomics inside one workgroup, none across workgroups, and two mask
+ * arrays so that a round reads only what the round before left (a problem gives the same integers, the round counts
+ * included, alone, in any batch, on either path, run after run; tests/hops_ref.py).
+ * src, dst, labels and the columns 0 .. 11 of desc [G, 15] int64 (once on the host, checked here; once on the device) are those
+ * of spadot_nhood_counts, the permuted labelings included.  Further columns:
+ *   12 first int of the problem in hops (-1: not asked for; otherwise the [n, K] hop distances of its FIRST labeling are written)
+ *   13 first int of the problem's slabs in scratch (checked: the sum of the slabs of the problems before; ignored on the LDS path)
+ *   14 kind: 0 label items -- item l of the problem is labeling l, set a = the nodes that carry label a, the class of a node its
+ *      label; 1 source items -- p0 = -1, ONE explicit labeling of n labels, L = ceil(n / 32), column 12 = -1 and K_max = 32:
+ *      item l has the sets {32 l + j}, j = 0 .. 31 (those past n empty), the class of a node is its label
+ * out: int64 [sum L, K_max, K_max, 3] per (set, class): the nodes of the class at a distance >= 1 of the set (reached), the
+ * sum of those distances (sumdist), those at distance 1 (adjacent); zeros for an empty set and outside the sets and classes of
+ * the item; written completely.  ecc: int32 [sum L, K_max] the largest distance from a set (0: nothing reached).  hops: int32
+ * [n_hops] (may be null when no problem asks): 0 for the members of a set, the distance for the nodes it reaches, -1 for the
+ * others.  status: int32 [sum L, 2] = (0, or 1 when the round cap n + 1 was reached: the other outputs of that item are then
+ * meaningless; rounds run: the largest distance + 1).
+ * A problem keeps its two mask arrays and its classes in LDS where 16640 + 8 n + (n rounded up to 16) <= lds_limit (at most
+ * 163840; larger values mean 163840: n <= 16 354) and otherwise in a slab of 2 n + ceil(n / 4) ints per item of `scratch`
+ * (int32 [n_scratch]; may be null when every problem fits); the work stays inside the workgroup's own slab.
+ * Return -22 for null or inconsistent arguments and -7, before any launch, outside the limits of spadot_nhood_counts. */
+int spadot_hop_sums(const int *src, const int *dst, const unsigned char *labels, const long long *desc_host,
+                    const long long *desc_dev, int G, int K_max, long long lds_limit, long long *out, int *ecc, int *hops,
+                    long long n_hops, int *status, unsigned *scratch, long long n_scratch, void *stream);
 
 /* ---------------------------------------------------------------- co-occurrence by distance (csrc/cooccur.hip)
  * N[a, b, t] = #{ordered pairs (i, j), i != j : lab[i] = a, lab[j] = b, d2(i, j) <= r2[t]} of P (spot set, labeling,

@@ -279,6 +279,7 @@ def model_lib():
         "spadot_gmm_estep": [vp, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp],
         "spadot_nhood_counts": [vp, vp, vp, vp, vp, ci, ci, ll, vp, vp],
         "spadot_territory_counts": [vp, vp, vp, vp, vp, ci, ci, ll, vp, vp, vp, ll, vp, vp, ll, vp],
+        "spadot_hop_sums": [vp, vp, vp, vp, vp, ci, ci, ll, vp, vp, vp, ll, vp, vp, ll, vp],
         "spadot_cooccur_counts": [vp, vp, vp, vp, vp, ci, ci, ci, vp, vp],
         "spadot_cooccur_null": [vp, vp, vp, vp, vp, ci, ci, ci, ci, ll, ci, ll, vp, vp],
         "spadot_ripley_counts": [vp, vp, vp, vp, vp, vp, vp, vp, vp, ll, ci, ci, ci, ci, ll, vp, vp],

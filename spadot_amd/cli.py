@@ -28,6 +28,8 @@
                                  [--n_iter 30000] [--device cuda:0]
     python -m spadot_amd territories --domains CSV [-o DIR] [--prefix P] [--k 6] [--n_perms 1000] [--seed 0] [--min_size 0]
                                      [--alpha 0.05] [--device cuda:0]
+    python -m spadot_amd centrality --domains CSV [-o DIR] [--prefix P] [--k 6] [--n_perms 200] [--seed 0] [--spots]
+                                    [--device cuda:0]
 
 `preprocess` runs SPARK-X feature selection and the scaling on the device (spadot_amd.preprocess).  The balancing rule's gene
 clusters come from K-means by default; `--gene_clusters louvain` clusters SCTransform Pearson residuals with Louvain as the
@@ -80,7 +82,12 @@ and noise are flat almost at once; a ranking by the scale of a pattern beside SP
 k-nearest-neighbour graph of every time point (how many, the largest, the stray single spots, a contiguity between 0 and 1),
 each against `--n_perms` random relabelings, the territory of every spot and whether it lies on a border; with `--min_size S`
 every piece of fewer than S spots is handed to the domain it touches most and the cleaned map is written as
-refined_domains.csv, which every `--domains` stage reads (spadot_amd.territories)."""
+refined_domains.csv, which every `--domains` stage reads (spadot_amd.territories).  `centrality` reads the domains
+table and measures how far apart things are along the tissue, in hops on the k-nearest-neighbour graph of every time point:
+per domain the group closeness and group degree centrality of squidpy's `gr.centrality_scores` and its eccentricity, per
+ordered pair of domains the mean number of hops from a spot of one to the nearest spot of the other, each against `--n_perms`
+random relabelings, per spot the hops to every domain and its depth inside its own; with `--spots` also the closeness and
+eccentricity of every single spot, the diameter, the radius and the centre of the tissue (spadot_amd.centrality)."""
 import argparse
 import os
 import sys
@@ -221,6 +228,24 @@ def build_parser():
     te.add_argument("--alpha", dest="alpha", type=float, default=0.05,
                     help="Level of the adjusted p-value below which a domain is called contiguous or fragmented. Default: 0.05")
     te.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
+
+    ce = sub.add_parser("centrality", help="Hop distances along the tissue: group closeness and degree centrality of every "
+                                           "spatial domain, the mean hops between every pair of domains, and how deep inside "
+                                           "its domain every spot sits.")
+    ce.add_argument("--domains", dest="domains", type=str, required=True,
+                    help="The domains.csv written by analyze: row, timepoint, kmeans, pixel_x, pixel_y.")
+    ce.add_argument("-o", "--output_dir", dest="output_dir", type=str,
+                    help="Output directory. Default: the same as where the domains table locates.")
+    ce.add_argument("--prefix", dest="prefix", type=str, default="", help="Prefix for the centrality tables. Default: ''")
+    ce.add_argument("--k", dest="k", type=int, default=6, help="Spatial neighbours per spot. Default: 6")
+    ce.add_argument("--n_perms", dest="n_perms", type=int, default=200,
+                    help="Random relabelings (domain sizes kept) behind the z-scores and p-values, 0 to 9999; 0: no null. "
+                         "Default: 200")
+    ce.add_argument("--seed", dest="seed", type=int, default=0, help="Seed of the relabelings. Default: 0")
+    ce.add_argument("--spots", dest="spots", action="store_true",
+                    help="Also a breadth-first search from every single spot: its closeness and eccentricity, the diameter, "
+                         "the radius and the centre spots of every time point.")
+    ce.add_argument("--device", dest="device", type=str, default="cuda:0", help="Device to use. Default: cuda:0")
 
     co = sub.add_parser("cooccurrence", help="Co-occurrence of the spatial domains by distance: for every pair of domains, how "
                                              "many pairs of spots lie within each radius and the ratio to what the "
@@ -508,6 +533,13 @@ def main(argv=None):
             sys.exit(2)
         from .territories import territories_stage
         territories_stage(args)
+    elif args.cmd_choice == "centrality":
+        if not _exists(args.domains):
+            print(f"SpaDOT centrality: the domains table does not exist: {args.domains}. Please make sure it is correctly "
+                  "specified.", file=sys.stderr)
+            sys.exit(2)
+        from .centrality import centrality_stage
+        centrality_stage(args)
     elif args.cmd_choice == "cooccurrence":
         if not _exists(args.domains):
             print(f"SpaDOT cooccurrence: the domains table does not exist: {args.domains}. Please make sure it is correctly "

@@ -1,4 +1,4 @@
-"""The launches of the analysis stages (silhouette, gmm, neighbors, territories, cooccurrence, autocorr, ligrec, hotspots, modules, ripley,
+"""The launches of the analysis stages (silhouette, gmm, neighbors, territories, centrality, cooccurrence, autocorr, ligrec, hotspots, modules, ripley,
 correlogram, embed, sepal) in
 libspadot_model.so (include/spadot_model.h).  A *_check refuses, before any launch, what the library would refuse or cannot see (ranges that only a
 reduction on the device knows: one host round trip); a *_launch hands over what the check returned.  CPU tensors raise."""
@@ -327,6 +327,91 @@ def territory_counts(src, dst, labels, desc, K_max, lds_limit=None):
     problem that needs more works in a slab of global scratch.  Returns (out, ids, sizes, status) as territory_launch does.
     ValueError, before any launch, outside the limits."""
     return territory_launch(src, dst, labels, territory_check(src, dst, labels, desc, K_max), K_max, lds_limit)
+
+
+HOP_DESC = 15
+HOP_LDS_BYTES = 163840
+HOP_FIXED = 16640                 # the per-(set, class) tables, eccentricities and flags of a workgroup, ahead of its per-node arrays
+HOP_SETS = 32                     # the source sets of one item: the bits of a mask
+HOP_LIMITS = (NHOOD_LIMITS + "; a source problem has one explicit labeling, ceil(n / 32) items and K_max = 32; a problem stays in "
+              "LDS where 16640 + 8 n + (n rounded up to 16) <= lds_limit <= 163840 bytes (9 bytes a node: n <= 16354) and works "
+              "in its scratch slab of 2 n + ceil(n / 4) ints per item otherwise")
+
+
+def hop_lds_bytes(n):
+    """The LDS bytes a problem of n nodes needs to stay on chip: the fixed tables, then the two masks (uint32) and the class byte."""
+    return HOP_FIXED + 8 * n + ((n + 15) & ~15)
+
+
+def hop_slab_ints(n):
+    return 2 * n + (n + 3) // 4
+
+
+def hop_check(src, dst, labels, desc, K_max):
+    """The refusals of hop_sums, before any launch: those of nhood_check on the columns 0 .. 11 (limits, then the range of the
+    edge ends and the largest label by reductions on the device, one host round trip), column 12 >= -1, column 14 in (0, 1) and,
+    for a source problem (column 14 = 1), one explicit labeling, ceil(n / 32) items, no hops and K_max = 32.  Returns the
+    descriptor with columns 10 and 11 filled in; ValueError otherwise."""
+    desc = _host_desc(desc, HOP_DESC, "problem")
+    if (desc[:, 12] < -1).any():
+        raise ValueError(f"problem {int(np.flatnonzero(desc[:, 12] < -1)[0])}: inconsistent descriptor (column 12 is -1 or the first "
+                         f"int in hops)")
+    for g, row in enumerate(desc.tolist()):
+        if row[14] not in (0, 1):
+            raise ValueError(f"problem {g}: inconsistent descriptor (column 14 is 0 for label items, 1 for source items)")
+        if row[14] == 1 and (row[6] != -1 or row[5] != (row[1] + HOP_SETS - 1) // HOP_SETS or row[12] != -1):
+            raise ValueError(f"problem {g}: a source problem has one explicit labeling, ceil(n / {HOP_SETS}) items and no hops "
+                             f"(got {row})")
+        if row[14] == 1 and int(K_max) != HOP_SETS:
+            raise ValueError(f"problem {g}: spadot_hop_sums takes source problems with K_max = {HOP_SETS} only (got {int(K_max)})")
+    seen = desc[:, :NHOOD_DESC].copy()
+    seen[desc[:, 14] == 1, 6] = 0                       # a source problem reads one labeling of n labels, as a permuted one does
+    try:
+        seen = nhood_check(src, dst, labels, seen, K_max)
+    except ValueError as e:
+        raise ValueError(str(e).replace("spadot_nhood_counts", "spadot_hop_sums")) from None
+    desc[:, 10], desc[:, 11] = seen[:, 10], seen[:, 11]
+    return desc
+
+
+def hop_launch(src, dst, labels, desc, K_max, lds_limit=None):
+    """The launch of hop_sums for a descriptor that hop_check has returned (the library checks it again, on the host).  Column
+    13, the slab offsets, is filled in here, the scratch tensor made and the descriptor uploaded.  Returns (out int64
+    [items, K_max, K_max, 3], ecc int32 [items, K_max], hops int32 of the length the descriptor's column 12 asks for, status
+    int32 [items, 2])."""
+    need_cuda(src, dst, labels)
+    desc = np.array(desc, dtype=np.int64, order="C", copy=True)
+    K_max, items = int(K_max), int(desc[:, 5].sum())
+    lds_limit = _lds_limit(lds_limit, HOP_LDS_BYTES)
+    slabs = n_hops = 0
+    for g in range(desc.shape[0]):
+        n, K, L = int(desc[g, 1]), int(desc[g, 3]), int(desc[g, 5])
+        if desc[g, 12] >= 0:
+            n_hops = max(n_hops, int(desc[g, 12]) + n * K)
+        if hop_lds_bytes(n) > lds_limit:
+            desc[g, 13] = slabs
+            slabs += L * hop_slab_ints(n)
+    dev = labels.device
+    out = torch.empty((items, K_max, K_max, 3), dtype=torch.int64, device=dev)
+    ecc = torch.empty((items, K_max), dtype=torch.int32, device=dev)
+    status = torch.empty((items, 2), dtype=torch.int32, device=dev)
+    hops = torch.empty(n_hops, dtype=torch.int32, device=dev)
+    scratch = torch.empty(slabs, dtype=torch.int32, device=dev)
+    desc_dev = torch.as_tensor(desc, device=dev)
+    launched(model_lib().spadot_hop_sums(_p(src), _p(dst), _p(labels), _host(desc), _p(desc_dev), int(desc.shape[0]), K_max,
+                                         lds_limit, _p(out), _p(ecc), _p(hops) if n_hops else None, n_hops, _p(status),
+                                         _p(scratch) if slabs else None, slabs, _stream()),
+             "spadot_hop_sums", HOP_LIMITS)
+    return out, ecc, hops, status
+
+
+def hop_sums(src, dst, labels, desc, K_max, lds_limit=None):
+    """The hop distances from every source set of many (graph, labeling) problems in ONE launch (include/spadot_model.h:
+    spadot_hop_sums).  src, dst int32 and labels uint8 device tensors, the graphs back to back; desc: int64 [G, 15] on the host
+    as the header lays it out (columns 10, 11 and 13 are filled in here).  lds_limit: the LDS bytes a workgroup may use (default
+    and at most 163840); a problem that needs more works in a slab of global scratch.  Returns (out, ecc, hops, status) as
+    hop_launch does.  ValueError, before any launch, outside the limits."""
+    return hop_launch(src, dst, labels, hop_check(src, dst, labels, desc, K_max), K_max, lds_limit)
 
 
 COOCCUR_MAX_K = 32

@@ -205,6 +205,23 @@ def plot_territories(path, pixel_x, pixel_y, labels, small, timepoint, min_size)
     fig.savefig(path)
 
 
+def plot_depth(path, pixel_x, pixel_y, depth, timepoint):
+    """{prefix}{tp}_centrality.png: the spots coloured by depth, the number of hops to the nearest spot of another domain (1: on
+    a border); a spot that reaches no other domain (depth -1) is drawn grey."""
+    fig = _figure((5.5, 5))
+    ax = fig.add_subplot(1, 1, 1)
+    x, y, depth = np.asarray(pixel_x), np.asarray(pixel_y), np.asarray(depth)
+    far = depth < 0
+    ax.scatter(x[far], y[far], s=10, color="lightgrey", linewidths=0)
+    sc = ax.scatter(x[~far], y[~far], s=10, c=depth[~far], cmap="viridis", vmin=1, vmax=max(int(depth.max()), 2), linewidths=0)
+    fig.colorbar(sc, ax=ax, label="hops to another domain")
+    ax.set_xlabel("pixel_x")
+    ax.set_ylabel("pixel_y")
+    ax.set_title("Depth, time point: {}".format(timepoint))
+    fig.tight_layout()
+    fig.savefig(path)
+
+
 def plot_nhood(path, zscore, timepoint):
     """{prefix}{tp}_nhood.png: the neighbourhood-enrichment z-scores of one time point as a heat map (domain by neighbor), on
     a diverging scale centred at 0; a cell without a z-score (no variance under permutation) stays blank."""
