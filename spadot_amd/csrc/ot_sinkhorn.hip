@@ -1751,8 +1751,9 @@ void choose_chunks(spadot_ot_solver *s) {
     s->nchunk = (s->I + s->rows_per_chunk - 1) / s->rows_per_chunk;
 }
 
-// Fused single-sweep pass is used when a row fits the register budget of one 1024-thread workgroup
+// Fused single-sweep pass is used when a row fits the register budget of one 512-thread workgroup (FUSED_THREADS)
 // and w fits LDS; SPADOT_OT_NO_FUSED=1 forces the two-sweep kernels (A/B runs, fallback tests).
+// tests/ot_pass_cases.py (fused_geometry_expected) restates this rule; keep the two in step.
 void choose_fused(spadot_ot_solver *s) {
     s->fused_vpt = 0;
     const char *off = getenv("SPADOT_OT_NO_FUSED");

@@ -242,6 +242,10 @@ class OTSolver:
                 "fused_pass": ms[4], "fused_col_fin": ms[5]}
 
     def fused_geometry(self):
+        """The band geometry of the fused single-sweep pass for this shape: 16-byte vectors per thread and row (vpt), rows
+        per group, workgroups and rows per workgroup; all zeros when the two-sweep kernels are used.  The rule (choose_fused
+        in csrc/ot_sinkhorn.hip) is restated for any shape and CU count by fused_geometry_expected in
+        tests/ot_pass_cases.py, which tests/test_ot_pass_edges_gpu.py holds this method to."""
         g = (ctypes.c_int * 4)()
         self.lib.spadot_ot_fused_geometry(self.h, g)
         return {"vpt": g[0], "rows_per_group": g[1], "workgroups": g[2], "rows_per_workgroup": g[3]}
